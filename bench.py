@@ -1,7 +1,19 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of nbdistributed_amd (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-sweep]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-sweep ...]]
+
+A plain run starts the workers, runs W warm-up and K timed trivial ``%%distributed`` cells, writes
+the last timed cell's outputs when ``--dump-outputs DIR`` is given (``DIR/cell_echo.npy``: the
+value every rank echoed, float64: the constant 2.0 of ``1 + 1``, since the headline is a
+control-plane latency and computes nothing else) and prints the result line.  On GPUs one last
+cell then has every rank load the HIP library as built and run one kernel with a known answer
+(``native_libs``: what the rank has mapped; a failure is ``native_error`` and exit status 3, the
+measured value still printed): the timed cells never reach that library, and a benchmark of this
+project must not pass on a build whose kernels do not load.  ``--full`` adds every other phase
+(process-group report, magic-path and real-IPython cells, all_reduce and its sweep, ``%%rank`` +
+broadcast, DDP, the notebook workload, the data-plane correctness checks); the ``--no-*``
+switches drop single phases of a full run.
 
 Two launch forms, one measurement:
 
@@ -18,17 +30,18 @@ Two launch forms, one measurement:
   never touches the GPU.
 
 Either way rank 0 (or the self-launching kernel) prints exactly ONE JSON line (value = trivial
-``%%distributed`` cell p50 round trip in ms, reference 111.6 ms; plus 1 GiB bf16 all_reduce
-algbw/busbw and the 1 KiB..1 GiB sweep).  Nothing here may hang silently:
+``%%distributed`` cell p50 round trip in ms, reference 111.6 ms; ``ms_per_step`` = mean round trip
+of the K timed cells; with ``--full`` also 1 GiB bf16 all_reduce algbw/busbw and the 1 KiB..1 GiB
+sweep).  Nothing here may hang silently:
 
 * ranks that do not all reach READY within ``NBD_BENCH_RENDEZVOUS_S`` (default 300 s) produce the
   line with ``"value": null`` and ``"error": "rendezvous: k/N ranks joined"``;
 * past ``NBD_BENCH_HARD_S`` (default 540 s) the line is printed from the last checkpointed phase
   with ``"partial": true``;
 * the exit status is non-zero whenever the line is partial or carries an error, and 5 when a
-  data-plane correctness check (``nbdistributed_amd.checks``: collectives against closed-form
-  values, nbd DDP against torch DDP, ZeRO-2, the graphed step, accelerate, ``%%rank`` +
-  broadcast) failed — ``"checks_passed"`` / ``"checks"`` in the line say which.
+  data-plane correctness check of a ``--full`` run (``nbdistributed_amd.checks``: collectives
+  against closed-form values, nbd DDP against torch DDP, ZeRO-2, the graphed step, accelerate,
+  ``%%rank`` + broadcast) failed — ``"checks_passed"`` / ``"checks"`` in the line say which.
 """
 from __future__ import annotations
 
@@ -63,6 +76,11 @@ def _args(argv=None):
     ap.add_argument("--gpus", type=int, default=None)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed cells, also run every other phase: process-group report, magic-path and "
+                         "real-IPython cells, all_reduce + sweep, broadcast, DDP, notebook workload, correctness checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed cell returned (every rank's echo) as DIR/cell_echo.npy")
     ap.add_argument("--sweep", action="store_true", default=True, help=argparse.SUPPRESS)  # the default now
     ap.add_argument("--no-sweep", dest="sweep", action="store_false",
                     help="skip the 1 KiB..1 GiB all_reduce bus-bandwidth sweep")
@@ -86,8 +104,13 @@ def _log(msg: str) -> None:
 
 
 def _phases_kw(a) -> dict:
+    dump = os.path.abspath(a.dump_outputs) if a.dump_outputs else None
+    if not a.full:  # a plain run: the timed cells (the headline figure) and nothing else
+        return dict(allreduce=False, sweep=False, ddp=False, bcast=False, notebook=False, checks=False, extras=False,
+                    dump_dir=dump, native_probe=True)
     return dict(allreduce=not a.no_allreduce, sweep=a.sweep, ar_bytes=a.ar_bytes, ddp=not a.no_ddp,
-                ddp_steps=a.ddp_steps, bcast=not a.no_bcast, notebook=not a.no_notebook, checks=not a.no_checks)
+                ddp_steps=a.ddp_steps, bcast=not a.no_bcast, notebook=not a.no_notebook, checks=not a.no_checks,
+                dump_dir=dump)
 
 
 def _snapshot(out: dict) -> dict:
@@ -141,7 +164,8 @@ class _Printer:
                 if res.get(k) is not None:
                     line[k] = res[k]
             # a failed correctness check makes the run fail (exit status), whatever was timed
-            bad = bool(res.get("partial") or why or line.get("error") or line.get("checks_passed") is False)
+            bad = bool(res.get("partial") or why or line.get("error") or line.get("checks_passed") is False
+                       or line.get("native_error"))
             if res.get("partial") or why:
                 line["partial"] = True
                 line["partial_reason"] = why or "coordinator ended before the last phase"
@@ -269,6 +293,10 @@ def attach_main(a) -> int:
                          ("--no-bcast", a.no_bcast), ("--no-notebook", a.no_notebook), ("--no-checks", a.no_checks)):
             if on:
                 cmd.append(flag)
+        if a.full:
+            cmd.append("--full")
+        if a.dump_outputs:
+            cmd += ["--dump-outputs", os.path.abspath(a.dump_outputs)]
         child = subprocess.Popen(cmd, stdin=subprocess.DEVNULL)
     from nbdistributed_amd import protocol as P
     from nbdistributed_amd.worker import worker_from_env
@@ -349,4 +377,12 @@ if __name__ == "__main__":
     code = main()
     sys.stdout.flush()
     sys.stderr.flush()
+    if code == 0 and not _under_launcher() and "--coordinator" not in sys.argv:
+        # a completed self-launched run holds no GPU and no stuck rank: leave through the interpreter,
+        # so that exit-time handlers (atexit, library destructors: profilers, coverage, loaders that
+        # report at exit) see the run.  Nothing may hang silently here either: if a leftover thread
+        # or handler holds the exit, SIGALRM's default action ends the process after 20 s.
+        signal.signal(signal.SIGALRM, signal.SIG_DFL)
+        signal.alarm(20)
+        sys.exit(0)
     os._exit(code)

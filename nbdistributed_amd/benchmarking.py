@@ -418,15 +418,32 @@ def bench_cells(session, steps: int, warmup: int, code: str = "1 + 1") -> Dict[s
     session.sync()
     lat = []
     t0 = time.perf_counter()
+    last = None
     for _ in range(steps):
         t = time.perf_counter()
-        session.execute(code, render=False)
+        last = session.execute(code, render=False)
         lat.append(time.perf_counter() - t)
     session.sync()
     total = time.perf_counter() - t0
     ms = [x * 1e3 for x in lat]
-    return {"p50_ms": statistics.median(ms), "p90_ms": _pct(ms, 0.9), "p99_ms": _pct(ms, 0.99), "min_ms": min(ms),
-            "mean_ms": statistics.fmean(ms), "max_ms": max(ms), "steps": steps, "total_s": total}
+    out = {"p50_ms": statistics.median(ms), "p90_ms": _pct(ms, 0.9), "p99_ms": _pct(ms, 0.99), "min_ms": min(ms),
+           "mean_ms": statistics.fmean(ms), "max_ms": max(ms), "steps": len(lat), "total_s": total}  # steps: latencies recorded
+    if last is not None:  # what the caller of the last timed cell received: every rank's echo
+        out["last_echo"] = [_echo(last.results[r]) for r in sorted(last.ranks)]
+    return out
+
+
+def dump_cell_outputs(cells: Dict[str, Any], path: str) -> Dict[str, Any]:
+    """Write what the last timed cell returned as ``path/cell_echo.npy``: one float64 per rank,
+    the value each rank echoed for the cell's last expression (``1 + 1`` -> 2.0).  The cell takes
+    no input but its own text, so two builds run with the same arguments are comparable value
+    for value."""
+    import numpy as np
+
+    arr = np.asarray([float(e) for e in cells.get("last_echo", [])], dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "cell_echo.npy"), arr)
+    return {"dir": path, "files": {"cell_echo.npy": list(arr.shape)}}
 
 
 def bench_cells_magic(session, steps: int, warmup: int, code: str = "1 + 1") -> Dict[str, Any]:
@@ -527,6 +544,31 @@ def bench_cells_ipython(ranks: List[int], steps: int = 200, warmup: int = 20, ti
 
 
 WORLD_CHECK = "(dist.get_world_size(), dist.get_backend(), rank)"
+
+# Last cell of a plain GPU run (after the timed cells and the dump, so the cells are timed in the
+# same worker state as ever): the trivial cells never reach the HIP library, so a plain run would
+# otherwise say nothing about the build it ran on.  The rank loads libnbd_ops.so as built (never
+# rebuilding here), runs one kernel whose result is known in closed form, and reports which of
+# the project's native libraries it has mapped.
+NATIVE_PROBE = """
+import nbdistributed_amd.ops as _nbd_ops
+if not _nbd_ops.load_library(build=False):
+    raise RuntimeError(f"native HIP library not loaded: {_nbd_ops._lib._load_error}")
+_nbd_s = _nbd_ops.tensor_summary(torch.arange(256, device=device, dtype=torch.float32))
+if (_nbd_s["count"], _nbd_s["sum"], _nbd_s["min"], _nbd_s["max"]) != (256, 32640.0, 0.0, 255.0):
+    raise RuntimeError(f"tensor_summary kernel: wrong result {_nbd_s}")
+sorted({_l.split()[-1] for _l in open("/proc/self/maps") if "/libnbd_" in _l})
+"""
+
+
+def bench_native(session) -> Dict[str, Any]:
+    """Run ``NATIVE_PROBE`` on every rank; raises (``DistributedExecutionError``) when a rank
+    cannot load the HIP library or its kernel answers wrongly.  Returns the mapped native
+    libraries per rank."""
+    import ast
+
+    res = session.execute(NATIVE_PROBE, render=False)
+    return {"per_rank": {str(r): ast.literal_eval(_echo(res.results[r])) for r in sorted(res.ranks)}}
 
 
 def bench_world(session) -> Dict[str, Any]:
@@ -867,11 +909,16 @@ CPU_AR_BYTES = int(os.environ.get("NBD_BENCH_CPU_AR_BYTES", str(1 << 20)))
 def run_all(session, steps: int, warmup: int, allreduce: bool = True, sweep: bool = False,
             ar_bytes: int = 1 << 30, ddp: bool = True, ddp_steps: int = 20, bcast: bool = True,
             notebook: bool = True, phase_timeout_s: float = 300.0, deadline_s: Optional[float] = None,
-            checkpoint=None, checks: bool = True) -> Dict[str, Any]:
+            checkpoint=None, checks: bool = True, extras: bool = True,
+            dump_dir: Optional[str] = None, native_probe: bool = False) -> Dict[str, Any]:
     """All phases under one global deadline (``deadline_s`` from now, default
     ``NBD_BENCH_DEADLINE_S`` = 420 s); ``checkpoint(out)`` is called after every phase so the
     caller can persist what has been measured (bench.py writes it where rank 0 reads it, even if
-    a later phase hangs)."""
+    a later phase hangs).  The timed trivial cells always run; ``extras`` adds the phases that
+    have no switch of their own (process-group report, magic-path and real-IPython cells), and
+    ``dump_dir`` receives the last timed cell's outputs (``dump_cell_outputs``).  ``native_probe``
+    (bench.py's plain run, whose cells never reach the HIP library) ends a GPU run with
+    ``bench_native``; the other phases load and check that library themselves."""
     n = session.world_size
     _ARM_T0[0] = time.monotonic()
     deadline = time.monotonic() + (DEFAULT_DEADLINE_S if deadline_s is None else deadline_s)
@@ -890,23 +937,29 @@ def run_all(session, steps: int, warmup: int, allreduce: bool = True, sweep: boo
         cells = bench_cells(session, steps, warmup)
         _log(f"cell p50 {cells['p50_ms']:.3f} ms")
         out: Dict[str, Any] = {"cell": cells}
+        if dump_dir:
+            out["dumped_outputs"] = dump_cell_outputs(cells, dump_dir)
         ckpt(out)
-        _phase(session, out, "world", lambda: bench_world(session), phase_timeout_s, deadline)
-        _log(f"phase 1b: {warmup}+{steps} trivial cells through the magic path (auto mode, ide_sync, renderer)")
-        _phase(session, out, "cell_magic", lambda: bench_cells_magic(session, steps, warmup), phase_timeout_s, deadline)
-        if "p50_ms" in out["cell_magic"]:
-            _log(f"magic-path cell p50 {out['cell_magic']['p50_ms']:.3f} ms")
-        ckpt(out)
-        if os.path.exists(IPYTHON_PY) and os.environ.get("NBD_BENCH_IPYTHON", "1") != "0":
-            _log(f"phase 1c: trivial cells through a real IPython kernel ({n} gloo worker(s))")
-            _phase(session, out, "cell_ipython",
-                   lambda: bench_cells_ipython([n], steps=max(steps, 50), warmup=warmup,
-                                               timeout_s=max(30.0, min(240.0, deadline - time.monotonic() - 5.0))),
-                   phase_timeout_s, deadline, 30.0)
-            ci = out["cell_ipython"].get(str(n), {}).get("auto") if isinstance(out["cell_ipython"], dict) else None
-            if ci:
-                _log(f"real-IPython cell p50 {ci['p50_ms']:.3f} ms")
+        if native_probe and session.ready.get(0, {}).get("cuda_available"):
+            _phase(session, out, "native", lambda: bench_native(session), min(phase_timeout_s, 60.0), deadline)
             ckpt(out)
+        if extras:
+            _phase(session, out, "world", lambda: bench_world(session), phase_timeout_s, deadline)
+            _log(f"phase 1b: {warmup}+{steps} trivial cells through the magic path (auto mode, ide_sync, renderer)")
+            _phase(session, out, "cell_magic", lambda: bench_cells_magic(session, steps, warmup), phase_timeout_s, deadline)
+            if "p50_ms" in out["cell_magic"]:
+                _log(f"magic-path cell p50 {out['cell_magic']['p50_ms']:.3f} ms")
+            ckpt(out)
+            if os.path.exists(IPYTHON_PY) and os.environ.get("NBD_BENCH_IPYTHON", "1") != "0":
+                _log(f"phase 1c: trivial cells through a real IPython kernel ({n} gloo worker(s))")
+                _phase(session, out, "cell_ipython",
+                       lambda: bench_cells_ipython([n], steps=max(steps, 50), warmup=warmup,
+                                                   timeout_s=max(30.0, min(240.0, deadline - time.monotonic() - 5.0))),
+                       phase_timeout_s, deadline, 30.0)
+                ci = out["cell_ipython"].get(str(n), {}).get("auto") if isinstance(out["cell_ipython"], dict) else None
+                if ci:
+                    _log(f"real-IPython cell p50 {ci['p50_ms']:.3f} ms")
+                ckpt(out)
         hang = os.environ.get("NBD_BENCH_FAULT_HANG")
         if hang:  # fault injection (tests): a cell that outlives the budget must not cost the line
             _phase(session, out, "fault_hang",
@@ -1080,6 +1133,13 @@ def result_line(res: Dict[str, Any], n: int, steps: int, warmup: int) -> Dict[st
     if "per_rank" in wd:
         line["rccl_world_size"] = {str(r): v["world_size"] for r, v in wd["per_rank"].items()}
         line["process_group_backend"] = wd["backends"][0] if len(wd["backends"]) == 1 else wd["backends"]
+    nat = res.get("native") or {}  # plain GPU runs: the project's native libraries each rank has mapped
+    if "per_rank" in nat:
+        line["native_libs"] = nat["per_rank"]
+    elif nat:
+        line["native_error"] = nat.get("error") or nat.get("skipped")
+    if res.get("dumped_outputs"):
+        line["dumped_outputs"] = res["dumped_outputs"]
     if res.get("aborted"):
         line["aborted_phase"] = res["aborted"]
     for k in ("ddp", "rank_broadcast", "notebook"):

@@ -29,7 +29,7 @@ or against an independent implementation:
   parameters (BASELINE config 3), every rank then holds rank 0's bytes.
 
 ``run_checks`` returns ``{"passed": bool, "failed": [...], "results": {...}, "detail": {...}}``;
-bench.py puts it in its JSON line and exits non-zero when anything failed.
+``bench.py --full`` puts it in its JSON line and exits non-zero when anything failed.
 """
 from __future__ import annotations
 

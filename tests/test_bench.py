@@ -67,6 +67,25 @@ def test_cells_phase_and_result_line(sess):
     assert line["higher_is_better"] is False and line["n_gpus"] == 2
 
 
+def test_steps_sets_the_number_of_timed_cells(sess, tmp_path):
+    """The plain run (bench.py without ``--full``) executes exactly warm-up + steps cells, counted
+    at the session, and times ``steps`` of them; no other phase sends anything."""
+    import numpy as np
+
+    ran, execute = [], sess.execute
+    sess.execute = lambda code, *a, **kw: (ran.append(code), execute(code, *a, **kw))[1]
+    seq0 = next(sess.comm._seq)  # every request to the ranks takes one sequence number
+    try:
+        res = B.run_all(sess, 7, 3, allreduce=False, sweep=False, ddp=False, bcast=False, notebook=False,
+                        checks=False, extras=False, dump_dir=str(tmp_path), native_probe=True)
+    finally:
+        del sess.execute
+    assert ran == ["1 + 1"] * 10  # (no GPU: no native probe)
+    assert next(sess.comm._seq) - seq0 - 1 == 10 + 2  # the cells and bench_cells' two %sync, nothing else
+    assert res["cell"]["steps"] == 7 and set(res) == {"cell", "dumped_outputs"}
+    assert (np.load(tmp_path / "cell_echo.npy") == np.array([2.0, 2.0])).all()
+
+
 def test_failed_phase_is_recorded_and_timeout_aborts_the_rest():
     class _Cfg:
         interrupt_abort_s = 0.0
@@ -96,11 +115,11 @@ def test_failed_phase_is_recorded_and_timeout_aborts_the_rest():
 @pytest.mark.parametrize("n", [1, 2])
 def test_bench_py_contract_cpu(n):
     if n == 1:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--full"]
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
                "--master-addr", "127.0.0.1", "--master-port", "29655", os.path.join(ROOT, "bench.py"),
-               "--gpus", str(n), "--steps", "20", "--warmup", "2"]
+               "--gpus", str(n), "--steps", "20", "--warmup", "2", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd="/tmp")
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, res.stdout[-2000:] + res.stderr[-3000:]
@@ -113,13 +132,43 @@ def test_bench_py_contract_cpu(n):
     assert d["launch"].startswith("self" if n == 1 else "attach")
 
 
+@pytest.mark.parametrize("n", [1, 2])
+def test_bench_py_plain_run_is_lean_and_dumps_outputs(n, tmp_path):
+    """Without ``--full`` only the timed cells run: ``--steps`` of them, ``ms_per_step`` their mean
+    round trip, no other phase in the line; ``--dump-outputs`` holds the last cell's echo per rank."""
+    import numpy as np
+
+    dump = tmp_path / "dump"
+    args = ["--gpus", str(n), "--steps", "7", "--warmup", "2", "--dump-outputs", str(dump)]
+    if n == 1:
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), *args]
+    else:
+        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
+               "--master-addr", "127.0.0.1", "--master-port", "29659", os.path.join(ROOT, "bench.py"), *args]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=str(tmp_path))
+    lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+    assert res.returncode == 0 and len(lines) == 1, res.stdout[-2000:] + res.stderr[-3000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == n and d["steps"] == 7 and d["warmup"] == 2
+    assert d["value"] > 0 and d["unit"] == "ms" and d["higher_is_better"] is False and d["dtype"] == "bf16"
+    assert d["metric"] == json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
+    assert d["cell_min_ms"] <= d["ms_per_step"] and d["cell_min_ms"] <= d["value"]
+    moved = ("cell_magic", "cell_ipython", "allreduce", "rccl_world_size", "checks", "ddp", "notebook",
+             "rank_broadcast")
+    assert not [k for k in d if k.startswith(moved)], sorted(d)
+    assert "7 trivial" in res.stderr and "phase 2" not in res.stderr and "phase 7" not in res.stderr
+    assert sorted(os.listdir(dump)) == ["cell_echo.npy"]
+    echo = np.load(dump / "cell_echo.npy")
+    assert echo.dtype == np.float64 and echo.shape == (n,) and (echo == 2.0).all()
+
+
 def _selflaunch(n, env_extra=None, timeout=300, args=()):
     """``python bench.py --gpus N`` with no torchrun variables: bench.py starts its own N workers."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
     env.update({"NBD_BENCH_IPYTHON": "0"}, **(env_extra or {}))
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "10", "--warmup", "2",
-           "--no-ddp", "--no-notebook", "--no-bcast", *args]
+           "--full", "--no-ddp", "--no-notebook", "--no-bcast", *args]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd="/tmp", env=env)
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
     return res, lines

@@ -55,6 +55,31 @@ def test_cell_latency_on_gpu_worker(gpu_session):
     assert lat[len(lat) // 2] < 0.005  # < 5 ms p50 (reference: 111.6 ms)
 
 
+def test_plain_bench_run_loads_the_native_libraries(gpu_session, tmp_path):
+    """bench.py's plain run on a GPU: exactly warm-up + steps trivial cells, the dump, then one last
+    cell that loads the HIP library, checks a kernel's answer and reports what the rank has mapped."""
+    import os
+
+    import numpy as np
+
+    from nbdistributed_amd import benchmarking as B
+
+    ran, execute = [], gpu_session.execute
+    gpu_session.execute = lambda code, *a, **kw: (ran.append(code), execute(code, *a, **kw))[1]
+    try:
+        res = B.run_all(gpu_session, 20, 2, allreduce=False, sweep=False, ddp=False, bcast=False, notebook=False,
+                        checks=False, extras=False, dump_dir=str(tmp_path), native_probe=True)
+    finally:
+        del gpu_session.execute
+    assert ran == ["1 + 1"] * 22 + [B.NATIVE_PROBE]  # 2 warm-up + 20 timed cells, then the probe; no other phase
+    assert set(res) == {"cell", "native", "dumped_outputs"}
+    line = B.result_line(res, 1, 20, 2)
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and "native_error" not in line
+    libs = {os.path.basename(p) for p in line["native_libs"]["0"]}
+    assert {"libnbd_ops.so", "libnbd_transport.so"} <= libs, line["native_libs"]
+    assert (np.load(tmp_path / "cell_echo.npy") == np.array([2.0])).all()
+
+
 def test_cell_gpu_time_reaches_the_timeline(gpu_session):
     # the end event is recorded after the reply and the time reported with a later cell
     code = ("a = torch.randn(4096, 4096, device=device)\n"

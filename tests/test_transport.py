@@ -26,11 +26,26 @@ def _drain_event(sock, kind=T.EV_CONNECTED, timeout=5.0):
     raise AssertionError(f"event {kind} not seen")
 
 
+@pytest.fixture
+def sock_dir(tmp_path):
+    """A directory for ipc sockets.  A unix socket path holds at most 107 bytes (``sun_path``);
+    pytest's ``tmp_path`` (temp root + user + test name) can be longer than that on its own."""
+    if len(str(tmp_path)) <= 60:
+        yield str(tmp_path)
+        return
+    d = tempfile.mkdtemp(prefix="nbd-")
+    if len(d) > 60:
+        shutil.rmtree(d, ignore_errors=True)
+        d = tempfile.mkdtemp(prefix="nbd-", dir="/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
 @pytest.fixture(params=["tcp", "ipc"])
-def endpoint(request, tmp_path):
+def endpoint(request, sock_dir):
     if request.param == "tcp":
         return "tcp://127.0.0.1:0"
-    return f"ipc://{tmp_path}/t.sock"
+    return f"ipc://{sock_dir}/t.sock"
 
 
 def test_router_dealer_roundtrip(endpoint):
@@ -162,8 +177,8 @@ def test_token_auth_rejects_wrong_token():
         s.close()
 
 
-def test_dealer_connects_before_router_binds(tmp_path):
-    ep = f"ipc://{tmp_path}/late.sock"
+def test_dealer_connects_before_router_binds(sock_dir):
+    ep = f"ipc://{sock_dir}/late.sock"
     d = T.Socket(T.DEALER, identity=b"early")
     d.connect(ep)
     d.send([b"queued before bind"])  # held until the handshake completes
@@ -204,8 +219,8 @@ def _run_child(code: str, timeout: float = 30) -> subprocess.CompletedProcess:
                           timeout=timeout)
 
 
-def test_signal_prefix_raises_sigint_in_busy_process(tmp_path):
-    ep = f"ipc://{tmp_path}/sig.sock"
+def test_signal_prefix_raises_sigint_in_busy_process(sock_dir):
+    ep = f"ipc://{sock_dir}/sig.sock"
     r = T.Socket(T.ROUTER)
     r.bind(ep)
     code = f"""
@@ -232,8 +247,8 @@ def test_signal_prefix_raises_sigint_in_busy_process(tmp_path):
     r.close()
 
 
-def test_fd_capture_streams_python_and_c_output(tmp_path):
-    ep = f"ipc://{tmp_path}/cap.sock"
+def test_fd_capture_streams_python_and_c_output(sock_dir):
+    ep = f"ipc://{sock_dir}/cap.sock"
     r = T.Socket(T.ROUTER)
     r.bind(ep)
     code = f"""
@@ -315,7 +330,7 @@ PY39 = "/opt/conda/bin/python3.9"
 
 
 @pytest.mark.skipif(not os.path.exists(PY39), reason="no python3.9 + pyzmq oracle")
-def test_wire_interop_with_libzmq(tmp_path):
+def test_wire_interop_with_libzmq(sock_dir):
     chk = subprocess.run([PY39, "-c", "import zmq"], capture_output=True)
     if chk.returncode != 0:
         pytest.skip("pyzmq not importable by the oracle interpreter")
@@ -335,9 +350,9 @@ def test_wire_interop_with_libzmq(tmp_path):
         time.sleep(0.3)
         r.send([b"worker_7", b"reply", b""])
         assert d.poll(3000); assert d.recv_multipart() == [b"reply", b""]
-        zr = ctx.socket(zmq.ROUTER); zr.bind("ipc://{tmp_path}/z.sock")
+        zr = ctx.socket(zmq.ROUTER); zr.bind("ipc://{sock_dir}/z.sock")
         od = T.Socket(T.DEALER, identity=b"worker_3", heartbeat_ivl_ms=50)
-        od.connect("ipc://{tmp_path}/z.sock")
+        od.connect("ipc://{sock_dir}/z.sock")
         od.send([b"hello", b"x" * 70000])
         assert zr.poll(3000); fr = zr.recv_multipart(); assert fr[0] == b"worker_3" and len(fr[2]) == 70000
         zr.send_multipart([b"worker_3", b"back"])
