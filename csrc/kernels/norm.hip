@@ -870,7 +870,9 @@ static void launch_bwd(bool res, const at::Tensor& x, const at::Tensor& dy, cons
   T* dxp = static_cast<T*>(dx.data_ptr());
   float* pgp = pg.data_ptr<float>();
   if constexpr (sizeof(T) == 2) {
-    if (C == 256 * N && bwd16_enabled()) {
+    // (x, dy, dres are checked 16-B aligned by the callers; a weight view may sit at 8 B: the
+    // forward falls back from its 16-B kernel there too, launch_fwd16)
+    if (C == 256 * N && bwd16_enabled() && ((uintptr_t)wp & 15) == 0) {
       if (res)
         hipLaunchKernelGGL((ln_bwd16_kernel<T, W, true, N, RMS>), dim3(nblk), dim3(NT), 0, st, xp, dyp, dr, wp, mean,
                            rstd, dxp, pgp, rows, (int)C, rpb);

@@ -1,5 +1,6 @@
 """GPU numerics: HIP flash attention (csrc/kernels/attn.hip) against a plain fp32 PyTorch
-reference of the same bf16 inputs — forward output, and dq/dk/dv through autograd."""
+reference of the same bf16 inputs — forward output, and dq/dk/dv through autograd.
+Per-tile bounds on structured inputs, every backward path: tests/test_gpu_attn_paths.py."""
 import pytest
 import torch
 

@@ -1,5 +1,6 @@
 """GPU numerics: HIP LayerNorm (+ fused residual add), column sums and the bias-grad Linear
-(csrc/kernels/norm.hip) against plain fp32 PyTorch references."""
+(csrc/kernels/norm.hip) against plain fp32 PyTorch references.
+Per-row bounds on structured inputs, every backward instantiation: tests/test_gpu_norm_paths.py."""
 import pytest
 import torch
 import torch.nn.functional as F
