@@ -48,6 +48,7 @@
 #include <vector>
 #include <type_traits>
 
+#include "host_api.h"
 #include "nbd_common.h"
 
 namespace nbd {

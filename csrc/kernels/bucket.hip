@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "host_api.h"
 #include "nbd_common.h"
 
 namespace nbd {

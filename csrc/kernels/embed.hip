@@ -30,6 +30,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "host_api.h"
 #include "nbd_common.h"
 
 namespace nbd {

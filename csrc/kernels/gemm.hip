@@ -51,6 +51,7 @@
 
 #include "gemm_common.h"
 #include "graddst.h"
+#include "host_api.h"
 
 namespace nbd {
 namespace gemm {

@@ -24,7 +24,7 @@ namespace graddst {
 
 // Register `dst` as `param`'s gradient destination (undefined dst: remove).  `param` is normally a
 // leaf (DDP's parameters); a non-leaf registered here — a kept compute-dtype cast of an fp32
-// master weight (autograd.hip CastGroupFn) — has no .grad, so its writes never accumulate.
+// master weight (cast_group.hip CastGroupFn) — has no .grad, so its writes never accumulate.
 void set(const at::Tensor& param, const at::Tensor& dst);
 
 // The registered destination of `param`'s gradient if this write may go there (else undefined).
@@ -35,7 +35,7 @@ at::Tensor claim(const at::Tensor& param, bool& acc);
 at::Tensor hand_back(const at::Tensor& param, const at::Tensor& dst, bool acc);
 
 // What claim() would return for `param` now, without handing it out (no pass bookkeeping, no
-// flush): the per-block backward graphs (autograd.hip) check their captured destinations with it.
+// flush): the per-block backward graphs (llama_block.hip) check their captured destinations with it.
 at::Tensor peek(const at::Tensor& param, bool& acc);
 
 // Claims made on this thread while a log is set are appended to it (nullptr stops recording).
@@ -49,6 +49,10 @@ void record_claims(std::vector<ClaimRecord>* log);
 // Undo the pass bookkeeping of recorded claims (a graph capture that failed: nothing it captured
 // ran, so the slices were never written and may be claimed again in this pass).
 void release(const std::vector<ClaimRecord>& claims);
+
+// The destination if it was handed out earlier in the current pass (its gradient is still in
+// flight to AccumulateGrad): a later contribution adds itself into it.  Empty tensor otherwise.
+at::Tensor grad_dest_join(const at::Tensor& param);
 
 }  // namespace graddst
 

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "graddst.h"
+#include "host_api.h"
 #include "nbd_common.h"
 
 namespace nbd {

@@ -167,7 +167,7 @@ NATIVE_CAST = os.environ.get("NBD_NATIVE_CAST", "1") != "0"
 
 def cast_group(dtype, ps):
     """``ps`` cast to ``dtype`` through one flat buffer, gradients cast back the same way: the C++
-    node (``torch.ops.nbd.cast_group_ag``, csrc/kernels/autograd.hip ``CastGroupFn``) on the GPU,
+    node (``torch.ops.nbd.cast_group_ag``, csrc/kernels/cast_group.hip ``CastGroupFn``) on the GPU,
     the Python ``_CastGroup`` otherwise (``NBD_NATIVE_CAST=0``: always)."""
     ps = list(ps)
     if NATIVE_CAST and ps[0].is_cuda and dtype in _SCALAR_TYPE and ops.native_available():
@@ -782,7 +782,7 @@ def native(hf_model, compute_dtype: Optional[torch.dtype] = torch.bfloat16, fuse
         block_graphs = 0
     if hasattr(m, "model") and isinstance(m.model, LlamaModel):
         m.model.block_graphs = int(block_graphs)
-    # the decoder blocks write the cast weights' gradients into kept buffers (autograd.hip
+    # the decoder blocks write the cast weights' gradients into kept buffers (cast_group.hip
     # CastGroupFn): their split-K and norm-column reductions can be queued and issued together
     # (graddst.h defer; the cast node's backward flushes them) — 4 launches per layer become 2
     if os.environ.get("NBD_GRAD_DEFER", "1") != "0" and ops.native_available():

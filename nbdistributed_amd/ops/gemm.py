@@ -522,8 +522,8 @@ def _pair_plan(M: int, N: int, K: int, epi1: int = EPI_NONE) -> int:
 
 
 def native_plan(kind: str, M: int, H: int, I: int, bias1: bool = False, bias2: bool = False) -> list:
-    """The int plan of ``torch.ops.nbd.{linear,mlp_gelu,mlp_swiglu}_ag`` (layout: autograd.hip),
-    cached per shape.  ``linear``: x [M, I] -> [M, H] (W [H, I]); MLPs: x [M, H], hidden I."""
+    """The int plan of ``torch.ops.nbd.{linear,mlp_gelu,mlp_swiglu}_ag`` (layout: csrc/kernels/ag_common.h
+    ``LinearPlan`` / ``MLPPlan``), cached per shape.  ``linear``: x [M, I] -> [M, H] (W [H, I]); MLPs: x [M, H], hidden I."""
     key = (kind, M, H, I, bias1, bias2)
     p = _PLANS.get(key)
     if p is not None:
@@ -728,7 +728,7 @@ def linear_any(x, weight, bias=None):
     return F.linear(x, weight, bias)
 
 
-# fused Llama decoder block (csrc/kernels/autograd.hip LlamaBlockFn): NBD_FUSED_BLOCK=0 runs the
+# fused Llama decoder block (csrc/kernels/llama_block.hip LlamaBlockFn): NBD_FUSED_BLOCK=0 runs the
 # per-op nodes instead (same kernels, same results)
 FUSED_BLOCK = os.environ.get("NBD_FUSED_BLOCK", "1") != "0"
 _BLOCK_PLANS: dict = {}
@@ -767,7 +767,7 @@ def llama_block(x, h, w_qkv, b_qkv, w_o, b_o, w_post, w_gu, w_down, w_next, n_he
 
 
 def block_graphs(enable=None) -> int:
-    """Per-block HIP graphs for the EAGER Llama step (``csrc/kernels/autograd.hip`` namespace
+    """Per-block HIP graphs for the EAGER Llama step (``csrc/kernels/llama_block.hip`` namespace
     ``bg``; off by default, ``NBD_BLOCK_GRAPHS=1`` turns it on at start).  Each fused decoder
     block's forward is captured once per (block, shape) after two eager calls and replayed from
     then on — one graph launch for its seven kernels.  The block's outputs then live in static
@@ -824,7 +824,7 @@ def block_graphs_memory(device=None) -> dict:
 
 def cast_buffers_memory() -> dict:
     """The kept compute-dtype casts of ``models.native()``'s fp32 master weights and their gradient
-    buffers (autograd.hip ``castbuf``): memory the framework holds between steps."""
+    buffers (cast_group.hip ``castbuf``): memory the framework holds between steps."""
     import torch
 
     _require()

@@ -1,4 +1,4 @@
-"""GPU: per-block HIP graphs for the eager Llama step (ops.block_graphs, csrc/kernels/autograd.hip
+"""GPU: per-block HIP graphs for the eager Llama step (ops.block_graphs, csrc/kernels/llama_block.hip
 namespace ``bg``).  The graphed block runs the eager block's kernels in the same order, so every
 loss, gradient and updated parameter must be bit-identical to graphs off — across optimizer steps
 (weights change in place under the graph), with DDP bucket gradients and no_sync accumulation, a

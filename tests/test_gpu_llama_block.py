@@ -1,4 +1,4 @@
-"""GPU: the fused Llama decoder block (one autograd node, csrc/kernels/autograd.hip LlamaBlockFn)
+"""GPU: the fused Llama decoder block (one autograd node, csrc/kernels/llama_block.hip LlamaBlockFn)
 against the per-op path (NBD_FUSED_BLOCK=0 behaviour) — same kernels in the same order, so the
 loss, logits and every parameter gradient must be bit-identical; plus DDP with the gradients in
 their bucket slices (graddst) and the fp32 PyTorch reference of the whole model."""

@@ -26,7 +26,7 @@ def _both(fn, *args):
             y = fn(*ins)
             gy = torch.randn(y.shape, device=y.device, generator=torch.Generator(device="cuda").manual_seed(5)).to(y.dtype)
             y.backward(gy)
-            res.append((y.detach(), [a.grad if a is not None and a.requires_grad else None for a in ins]))
+            res.append((y.detach(), [a.grad if a is not None else None for a in ins]))
         finally:
             G.NATIVE_AUTOGRAD = True
     return res
@@ -68,6 +68,31 @@ def test_linear_native_matches_python_and_reference(M, N, K, bias, x_grad):
         assert rel(nat[1][0], xr.grad) < 2e-2
     if bias:
         assert rel(nat[1][2], br.grad) < 2e-2
+
+
+def test_linear_frozen_weight():
+    """A frozen weight: the backward is the separate dgrad product plus db = Σ dy (the `nx && !nw`
+    arm of ag_common.h linear_bwd_core).  y and dx bit-identical between the native and the Python
+    node; db only against the fp32 reference: the two nodes reduce it differently (fp32 at::sum
+    vs nbd::colsum)."""
+    M, N, K = 128, 128, 64
+    torch.manual_seed(M + N)
+    x = _rand(2, M // 2, K)
+    w = _rand(N, K, scale=K ** -0.5, grad=False)
+    b = _rand(N, scale=0.1)
+    nat, py = _both(G.gemm_linear, x, w, b)
+    assert torch.equal(nat[0], py[0])
+    assert torch.equal(nat[1][0], py[1][0])
+    assert nat[1][1] is None and py[1][1] is None  # w.grad
+    xr, br = x.detach().float().requires_grad_(), b.detach().float().requires_grad_()
+    yr = F.linear(xr, w.detach().float(), br)
+    yr.backward(torch.randn(yr.shape, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
+                .to(torch.bfloat16).float())
+    rel = lambda a, r: ((a.float() - r).abs().max() / r.abs().max()).item()  # noqa: E731
+    for got in (nat, py):
+        assert rel(got[0], yr) < 2e-2
+        assert rel(got[1][0], xr.grad) < 2e-2
+        assert rel(got[1][2], br.grad) < 2e-2
 
 
 @pytest.mark.parametrize("M,H,I", [(8192, 768, 3072), (512, 256, 1024)])
