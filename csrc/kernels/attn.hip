@@ -31,6 +31,11 @@
 // registers; K/Q tiles between the global load and the LDS store, one thread holding both halves
 // of a row chunk) and dQ/dK get the transpose rotation in the store epilogue — the packed
 // projection stays unrotated and no separate rotary kernels or gradient copies run.
+// Packed rows (SEG, causal only): several documents share a row; query i sees key j iff
+// kstart[i] <= j <= i, equivalently j <= i < qend[j] (packed.hip builds both arrays, non-decreasing
+// along the row).  The query-on-lane kernels (forward, dQ) carry kstart, the key-on-lane one
+// (dK/dV) carries qend; tile loops start / stop at the workgroup's bound, waves skip tiles wholly
+// outside theirs, and the compare is paid only in the 32x32 blocks a document boundary crosses.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -214,10 +219,15 @@ struct Stage2 {
 };
 
 // ============================================================================ forward
-template <bool CAUSAL>
+// the forward's running maximum of a lane that has seen no key yet (SEG): see fwd_kernel
+constexpr float kSegFloor = -3.0e38f;
+
+template <bool CAUSAL, bool SEG = false>
 __global__ __launch_bounds__(NT, 2) void fwd_kernel(View q, View k, View v, MView o, float* __restrict__ lse,
                                                      int H, int T, int nblk, float sc2, int group, Rope rp,
-                                                     const int* __restrict__ order) {
+                                                     const int* __restrict__ order,
+                                                     const int* __restrict__ kstart = nullptr) {
+  static_assert(!SEG || CAUSAL, "the document mask is causal");
   __shared__ __attribute__((aligned(16))) uint16_t Ks[TILE * RS];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[TILE * RSV];
   // work item (heaviest first under a causal mask); `order` places the items on the CUs (host: block_order)
@@ -234,17 +244,35 @@ __global__ __launch_bounds__(NT, 2) void fwd_kernel(View q, View k, View v, MVie
   for (int s = 0; s < 4; ++s) qf[s] = ld16(q.row(b, hh, qi) + 16 * s + 8 * h);
   if (rp.cos != nullptr) rope_frag(qf, rp, qi, h);
   f16x acc_o[2] = {zero16(), zero16()};
-  float m = -INFINITY, l = 0.f;
+  // SEG: a wave can hold queries of two documents, and for the later document's lanes an early
+  // tile is fully masked.  With m = -inf there, `mn > m + kDeferLog2` is false, nmn = +inf and
+  // exp2(fmaf(-inf, sc2, +inf)) is NaN for good.  Choice: m starts at a finite floor below every
+  // score.  A lane that has seen no key keeps m = floor (mn = max(floor, -inf)), its p are
+  // exp2(-inf) = 0 and a wave-wide rescale multiplies its l = 0 and O = 0 by exp2(0) = 1; at its
+  // first key mn > floor + kDeferLog2 holds and alpha = exp2(floor - mn) = 0 exactly, as
+  // exp2(-inf - mn) is without SEG — so trivial bounds give the unpacked kernel's bits.
+  float m = SEG ? kSegFloor : -INFINITY, l = 0.f;
   const int ntiles = CAUSAL ? (qb * BLK + BLK) / TILE : T / TILE;
+  // SEG: ks = this lane's first visible key; ks0 / ksl = the wave's smallest / largest (the array
+  // is non-decreasing); tb = the workgroup's first tile with a visible key (clamped: a bound is
+  // never trusted for addressing) — where the sweep and its first prefetch start
+  int ks = 0, ks0 = 0, ksl = 0, tb = 0;
+  if constexpr (SEG) {
+    const int* kr = kstart + (int64_t)b * T;
+    ks = kr[qi];
+    ks0 = __builtin_amdgcn_readfirstlane(kr[q0]);
+    ksl = __builtin_amdgcn_readfirstlane(kr[q0 + 31]);
+    tb = min(max(kr[qb * BLK], 0), qb * BLK) / TILE;
+  }
   StagePair sk;
   Stage2 sv;
-  sk.load(k.row(b, kh, 0), k.st, tid);
-  sv.load(v.row(b, kh, 0), v.st, tid);
-  sk.rope(rp, 0, tid);
+  sk.load(k.row(b, kh, tb * TILE), k.st, tid);
+  sv.load(v.row(b, kh, tb * TILE), v.st, tid);
+  sk.rope(rp, tb * TILE, tid);
   sk.store(Ks, RS, tid);
   sv.store(Vs, RSV, tid);
   __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = tb; t < ntiles; ++t) {
     if (t + 1 < ntiles) {  // issue the next tile's loads now, write them after this tile
       sk.load(k.row(b, kh, (t + 1) * TILE), k.st, tid);
       sv.load(v.row(b, kh, (t + 1) * TILE), v.st, tid);
@@ -278,6 +306,13 @@ __global__ __launch_bounds__(NT, 2) void fwd_kernel(View q, View k, View v, MVie
 #pragma unroll
             for (int i = 0; i < 16; ++i)
               if (k0 + kb * 32 + crow(i, h) > qi) sacc[kb][i] = -INFINITY;
+          }
+          if constexpr (SEG) {
+            if (k0 + kb * 32 < ksl) {  // the block holds a key before some query's document
+#pragma unroll
+              for (int i = 0; i < 16; ++i)
+                if (k0 + kb * 32 + crow(i, h) < ks) sacc[kb][i] = -INFINITY;
+            }
           }
         }
 #pragma unroll
@@ -330,8 +365,10 @@ __global__ __launch_bounds__(NT, 2) void fwd_kernel(View q, View k, View v, MVie
         }
       }
     };
-    if (!CAUSAL || k0 <= q0 + 31) {
-      if (CAUSAL && k0 + TILE - 1 > q0)
+    // (SEG: a tile whose last key lies before every document of the wave is skipped; one that
+    // holds a key before some query's document takes the masked body)
+    if ((!CAUSAL || k0 <= q0 + 31) && (!SEG || k0 + TILE - 1 >= ks0)) {
+      if (CAUSAL && (k0 + TILE - 1 > q0 || (SEG && k0 < ksl)))
         tile_body(std::true_type{});
       else
         tile_body(std::false_type{});
@@ -399,11 +436,11 @@ __device__ __forceinline__ void tile_delta(const Stage2& dO, const Stage2& O, fl
 // FD (fused δ, short sequences): δ = Σ_d dO·O is computed from the staged dO tile and an O tile
 // loaded beside it, instead of by bwd_pre_kernel — one launch less where each (query head, tile)
 // is swept by one key block anyway (T ≤ 256).
-template <bool CAUSAL, bool FD>
+template <bool CAUSAL, bool FD, bool SEG>
 __device__ __forceinline__ void dkdv_body(int blk, int nblocks, View q, View k, View v, View dout, View out,
                                           const float* __restrict__ lse, const float* __restrict__ delta, MView dk,
                                           MView dv, int H, int T, int nblk, float sc2, float scale, int group,
-                                          Rope rp, int gsplit, int64_t split_stride) {
+                                          Rope rp, int gsplit, int64_t split_stride, const int* __restrict__ qend) {
   // H = key/value heads; query heads hq = kvh·group + g, g < group
   __shared__ __attribute__((aligned(16))) uint16_t Qs[TILE * RS];
   __shared__ __attribute__((aligned(16))) uint16_t Os[TILE * RS];  // dO tile
@@ -428,7 +465,19 @@ __device__ __forceinline__ void dkdv_body(int blk, int nblocks, View q, View k, 
   if (rp.cos != nullptr) rope_frag(kf, rp, ki, h);
   f16x dvt[2] = {zero16(), zero16()}, dkt[2] = {zero16(), zero16()};
   const int t0 = CAUSAL ? (kb0 * BLK) / TILE : 0;
-  const int nt = T / TILE;
+  // SEG: qe = one past the last query that sees this lane's key (the one bound a lane carries);
+  // qe0 / qel = the wave's smallest / largest (the array is non-decreasing); the sweep stops at
+  // the tile of the block's last such query (clamped to the row: a bound is never trusted for
+  // addressing)
+  int qe = 0, qe0 = 0, qel = 0;
+  int nt = T / TILE;
+  if constexpr (SEG) {
+    const int* qr = qend + (int64_t)b * T;
+    qe = qr[ki];
+    qe0 = __builtin_amdgcn_readfirstlane(qr[key0]);
+    qel = __builtin_amdgcn_readfirstlane(qr[key0 + 31]);
+    nt = min(nt, max((qr[kb0 * BLK + BLK - 1] + TILE - 1) / TILE, t0 + 1));
+  }
   for (int g = split * gpw; g < (split + 1) * gpw; ++g) {
     const int hq = kvh * group + g;
     const float* lse_bh = lse + ((int64_t)b * Hq + hq) * T;
@@ -464,11 +513,14 @@ __device__ __forceinline__ void dkdv_body(int blk, int nblocks, View q, View k, 
         }
       }
       const int qt0 = t * TILE;
-      if (!CAUSAL || qt0 + TILE - 1 >= key0) {
+      if ((!CAUSAL || qt0 + TILE - 1 >= key0) && (!SEG || qt0 < qel)) {
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
           const int qr0 = qt0 + qb * 32;
           if (CAUSAL && qr0 + 31 < key0) continue;  // this 32-query block sees none of our keys
+          // SEG: nor does a block past the document of the wave's last key (its largest bound:
+          // the skip is wave-uniform)
+          if (SEG && qr0 >= qel) continue;
           // S[q][key] = Q . K^T (key on the lane); dP starts from -δ (row constant as the initial
           // accumulator: dS = P·(dP − δ) is then one multiply)
           f16x sacc = zero16(), dp;
@@ -486,6 +538,14 @@ __device__ __forceinline__ void dkdv_body(int blk, int nblocks, View q, View k, 
 #pragma unroll
             for (int i = 0; i < 16; ++i)
               if ((i & 3) + 8 * (i >> 2) < thr) sacc[i] = -INFINITY;
+          }
+          if constexpr (SEG) {  // queries of a later document: only in blocks that hold one
+            if (__builtin_amdgcn_readfirstlane((int)(qr0 + 31 >= qe0))) {
+              const int thr = qe - qr0 - 4 * h;  // masked where (i&3) + 8(i>>2) >= thr
+#pragma unroll
+              for (int i = 0; i < 16; ++i)
+                if ((i & 3) + 8 * (i >> 2) >= thr) sacc[i] = -INFINITY;
+            }
           }
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
@@ -538,10 +598,11 @@ __device__ __forceinline__ void dkdv_body(int blk, int nblocks, View q, View k, 
 }
 
 // ============================================================================ backward: dQ
-template <bool CAUSAL, bool FD>
+template <bool CAUSAL, bool FD, bool SEG>
 __device__ __forceinline__ void dq_body(int blk, int nblocks, View q, View k, View v, View dout, View out,
                                         const float* __restrict__ lse, const float* __restrict__ delta, MView dq,
-                                        int H, int T, int nblk, float sc2, float scale, int group, Rope rp) {
+                                        int H, int T, int nblk, float sc2, float scale, int group, Rope rp,
+                                        const int* __restrict__ kstart) {
   __shared__ __attribute__((aligned(16))) uint16_t Ks[TILE * RS];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[TILE * RS];
   const int per = nblocks / nblk;
@@ -578,21 +639,29 @@ __device__ __forceinline__ void dq_body(int blk, int nblocks, View q, View k, Vi
 #pragma unroll
   for (int i = 0; i < 16; ++i) ndl[i] = -dl;
   const int ntiles = CAUSAL ? (qb * BLK + BLK) / TILE : T / TILE;
+  int ks = 0, ks0 = 0, ksl = 0, tb = 0;  // SEG: the lane's, the wave's and the workgroup's bounds as in fwd_kernel
+  if constexpr (SEG) {
+    const int* kr = kstart + (int64_t)b * T;
+    ks = kr[qi];
+    ks0 = __builtin_amdgcn_readfirstlane(kr[q0]);
+    ksl = __builtin_amdgcn_readfirstlane(kr[q0 + 31]);
+    tb = min(max(kr[qb * BLK], 0), qb * BLK) / TILE;
+  }
   StagePair sk;
   Stage2 sv;
-  sk.load(k.row(b, kh, 0), k.st, tid);
-  sv.load(v.row(b, kh, 0), v.st, tid);
-  sk.rope(rp, 0, tid);
+  sk.load(k.row(b, kh, tb * TILE), k.st, tid);
+  sv.load(v.row(b, kh, tb * TILE), v.st, tid);
+  sk.rope(rp, tb * TILE, tid);
   sk.store(Ks, RS, tid);
   sv.store(Vs, RS, tid);
   __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
+  for (int t = tb; t < ntiles; ++t) {
     if (t + 1 < ntiles) {
       sk.load(k.row(b, kh, (t + 1) * TILE), k.st, tid);
       sv.load(v.row(b, kh, (t + 1) * TILE), v.st, tid);
     }
     const int k0 = t * TILE;
-    if (!CAUSAL || k0 <= q0 + 31) {
+    if ((!CAUSAL || k0 <= q0 + 31) && (!SEG || k0 + TILE - 1 >= ks0)) {
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         const int kr0 = k0 + kb * 32;
@@ -612,6 +681,14 @@ __device__ __forceinline__ void dq_body(int blk, int nblocks, View q, View k, Vi
 #pragma unroll
           for (int i = 0; i < 16; ++i)
             if ((i & 3) + 8 * (i >> 2) > thr) sacc[i] = -INFINITY;
+        }
+        if constexpr (SEG) {  // keys before some query's document: only in blocks that hold one
+          if (__builtin_amdgcn_readfirstlane((int)(kr0 < ksl))) {
+            const int thr = ks - kr0 - 4 * h;  // masked where (i&3) + 8(i>>2) < thr
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+              if ((i & 3) + 8 * (i >> 2) < thr) sacc[i] = -INFINITY;
+          }
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -652,20 +729,23 @@ __device__ __forceinline__ void dq_body(int blk, int nblocks, View q, View k, Vi
 // are independent, and for short sequences (SmolLM2: T = 128) neither fills the chip alone.
 // (Pairing complementary causal blocks in one workgroup — key blocks kb and nblk-1-kb, query
 // blocks qb and nblk-1-qb — was measured 14 % slower at B8 H12 T1024: docs/FINDINGS.md §31.)
-template <bool CAUSAL, bool FD>
+template <bool CAUSAL, bool FD, bool SEG = false>
 __global__ __launch_bounds__(NT, 2) void bwd_kernel(View q, View k, View v, View dout, View out,
                                                      const float* __restrict__ lse,
                                                      const float* __restrict__ delta, MView dq, MView dk, MView dv,
                                                      int Hq, int Hkv, int T, int nblk, float sc2, float scale,
                                                      int group, Rope rp, int nkv, int gsplit, int64_t split_stride,
-                                                     const int* __restrict__ order) {
+                                                     const int* __restrict__ order,
+                                                     const int* __restrict__ kstart = nullptr,
+                                                     const int* __restrict__ qend = nullptr) {
+  static_assert(!SEG || CAUSAL, "the document mask is causal");
   const int item = order != nullptr ? order[blockIdx.x] : (int)blockIdx.x;
   if (item < nkv)
-    dkdv_body<CAUSAL, FD>(item, nkv, q, k, v, dout, out, lse, delta, dk, dv, Hkv, T, nblk, sc2, scale, group, rp,
-                          gsplit, split_stride);
+    dkdv_body<CAUSAL, FD, SEG>(item, nkv, q, k, v, dout, out, lse, delta, dk, dv, Hkv, T, nblk, sc2, scale, group, rp,
+                               gsplit, split_stride, qend);
   else
-    dq_body<CAUSAL, FD>(item - nkv, gridDim.x - nkv, q, k, v, dout, out, lse, delta, dq, Hq, T, nblk, sc2, scale,
-                        group, rp);
+    dq_body<CAUSAL, FD, SEG>(item - nkv, gridDim.x - nkv, q, k, v, dout, out, lse, delta, dq, Hq, T, nblk, sc2, scale,
+                             group, rp, kstart);
 }
 
 // dk/dv[b, h, t, :] = Σ_s part[s][b][h][t][:] (fp32 sum of the gsplit partials); 8 elements per thread
@@ -852,9 +932,25 @@ static Rope rope_of(const c10::optional<at::Tensor>& c, const c10::optional<at::
   return Rope{c->data_ptr<float>(), s->data_ptr<float>()};
 }
 
-std::tuple<at::Tensor, at::Tensor> attn_fwd_hip(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                                                bool causal, double scale, const c10::optional<at::Tensor>& rope_cos,
-                                                const c10::optional<at::Tensor>& rope_sin) {
+// a [B, T] int32 bound array of packed.hip (kstart or qend)
+static const int* bound_of(const at::Tensor& t, const at::Tensor& q, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.get_device() == q.get_device() && t.scalar_type() == at::kInt && t.is_contiguous() &&
+                  t.dim() == 2 && t.size(0) == q.size(0) && t.size(1) == q.size(2),
+              "attn: ", name, " must be a contiguous int32 [B, T] tensor on q's device (ops.packed_bounds)");
+  return t.data_ptr<int>();
+}
+
+// Packed dispatch (bounds != nullptr; causal only).  The forward has one path per mask (no key
+// split exists here), so packing adds no second one.  The heaviest-first order and the LPT tables
+// are built from the causal weights: still a valid permutation under packing, merely no longer the
+// best one.  RoPE needs nothing: the kernels rotate by the row index t, not by position_ids[t],
+// and a score depends only on the difference of the two positions — for any per-frequency
+// inv_freq, Llama-3 scaling included — which inside a document is the same either way (mask.hip
+// leans on the same argument).
+static std::tuple<at::Tensor, at::Tensor> fwd_impl(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                                   bool causal, double scale,
+                                                   const c10::optional<at::Tensor>& rope_cos,
+                                                   const c10::optional<at::Tensor>& rope_sin, const int* kstart) {
   check_shapes(q, k, v);
   const Rope rp = rope_of(rope_cos, rope_sin, q.size(2));
   const int B = q.size(0), H = q.size(1), T = q.size(2);
@@ -873,7 +969,9 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_hip(const at::Tensor& q, const at::T
     // item k: query block nblk - 1 - k / (B·H), 2·(that + 1) key tiles
     const int* order = nullptr;
     if (nblk > 1) {
-      static const int slots = resident_blocks(fwd_kernel<true>, fwd_pad(), "NBD_ATTN_FWD_SLOTS");
+      static const int slots_causal = resident_blocks(fwd_kernel<true>, fwd_pad(), "NBD_ATTN_FWD_SLOTS");
+      static const int slots_packed = resident_blocks(fwd_kernel<true, true>, fwd_pad(), "NBD_ATTN_FWD_SLOTS");
+      const int slots = kstart != nullptr ? slots_packed : slots_causal;
       const int BH = B * H;
       order = block_order(
           {0, BH, nblk},
@@ -884,20 +982,40 @@ std::tuple<at::Tensor, at::Tensor> attn_fwd_hip(const at::Tensor& q, const at::T
           },
           slots, q.get_device(), st);
     }
-    hipLaunchKernelGGL((fwd_kernel<true>), grid, dim3(NT), fwd_pad(), st, qv, kv, vv, ov, lse.data_ptr<float>(), H, T, nblk,
-                       sc2, group, rp, order);
+    if (kstart != nullptr)
+      hipLaunchKernelGGL((fwd_kernel<true, true>), grid, dim3(NT), fwd_pad(), st, qv, kv, vv, ov, lse.data_ptr<float>(), H,
+                         T, nblk, sc2, group, rp, order, kstart);
+    else
+      hipLaunchKernelGGL((fwd_kernel<true>), grid, dim3(NT), fwd_pad(), st, qv, kv, vv, ov, lse.data_ptr<float>(), H, T,
+                         nblk, sc2, group, rp, order, static_cast<const int*>(nullptr));
   } else {
+    TORCH_CHECK(kstart == nullptr, "attn: the document mask is causal");
     hipLaunchKernelGGL((fwd_kernel<false>), grid, dim3(NT), fwd_pad(), st, qv, kv, vv, ov, lse.data_ptr<float>(), H, T, nblk,
-                       sc2, group, rp, static_cast<const int*>(nullptr));
+                       sc2, group, rp, static_cast<const int*>(nullptr), static_cast<const int*>(nullptr));
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
   return {o, lse};
 }
 
-void attn_bwd_hip(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
-                  const at::Tensor& out, const at::Tensor& lse, bool causal, double scale, const at::Tensor& dq,
-                  const at::Tensor& dk, const at::Tensor& dv, const c10::optional<at::Tensor>& rope_cos,
-                  const c10::optional<at::Tensor>& rope_sin, const c10::optional<at::Tensor>& delta_in) {
+std::tuple<at::Tensor, at::Tensor> attn_fwd_hip(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                                bool causal, double scale, const c10::optional<at::Tensor>& rope_cos,
+                                                const c10::optional<at::Tensor>& rope_sin) {
+  return fwd_impl(q, k, v, causal, scale, rope_cos, rope_sin, nullptr);
+}
+
+std::tuple<at::Tensor, at::Tensor> attn_fwd_packed_hip(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                                       double scale, const c10::optional<at::Tensor>& rope_cos,
+                                                       const c10::optional<at::Tensor>& rope_sin,
+                                                       const at::Tensor& kstart) {
+  TORCH_CHECK(q.dim() == 4, "attn: q must be [B, H, T, 64]");
+  return fwd_impl(q, k, v, true, scale, rope_cos, rope_sin, bound_of(kstart, q, "kstart"));
+}
+
+static void bwd_impl(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                     const at::Tensor& out, const at::Tensor& lse, bool causal, double scale, const at::Tensor& dq,
+                     const at::Tensor& dk, const at::Tensor& dv, const c10::optional<at::Tensor>& rope_cos,
+                     const c10::optional<at::Tensor>& rope_sin, const c10::optional<at::Tensor>& delta_in,
+                     const int* kstart, const int* qend) {
   check_shapes(q, k, v);
   const Rope rp = rope_of(rope_cos, rope_sin, q.size(2));
   TORCH_CHECK(dout.sizes() == q.sizes() && out.sizes() == q.sizes() && dq.sizes() == q.sizes() &&
@@ -972,17 +1090,22 @@ void attn_bwd_hip(const at::Tensor& dout, const at::Tensor& q, const at::Tensor&
         },
         slots, q.get_device(), st);
   };
-#define NBD_BWD(C_, F_, O_)                                                                                  \
-  hipLaunchKernelGGL((bwd_kernel<C_, F_>), dim3((unsigned)(nkv + nq)), dim3(NT), bwd_pad(), st, qv, kv, vv, dov, ov,   \
-                     lse.data_ptr<float>(), dptr, dqv, dkw, dvw, H, Hkv, T, nblk, sc2, (float)scale, group, rp, nkv, \
-                     gsplit, split_stride, O_)
+#define NBD_BWD(C_, F_, S_, O_)                                                                               \
+  hipLaunchKernelGGL((bwd_kernel<C_, F_, S_>), dim3((unsigned)(nkv + nq)), dim3(NT), bwd_pad(), st, qv, kv, vv, dov, \
+                     ov, lse.data_ptr<float>(), dptr, dqv, dkw, dvw, H, Hkv, T, nblk, sc2, (float)scale, group, rp,  \
+                     nkv, gsplit, split_stride, O_, kstart, qend)
   const int* none = nullptr;
-  if (causal) {
-    if (fd) NBD_BWD(true, true, causal_order(bwd_kernel<true, true>));
-    else NBD_BWD(true, false, causal_order(bwd_kernel<true, false>));
+  TORCH_CHECK((kstart == nullptr) == (qend == nullptr) && (kstart == nullptr || causal),
+              "attn_bwd: the document mask takes both bounds and is causal");
+  if (kstart != nullptr) {  // packed rows: the δ paths and the GQA split are those of the causal kernels
+    if (fd) NBD_BWD(true, true, true, causal_order(bwd_kernel<true, true, true>));
+    else NBD_BWD(true, false, true, causal_order(bwd_kernel<true, false, true>));
+  } else if (causal) {
+    if (fd) NBD_BWD(true, true, false, causal_order(bwd_kernel<true, true>));
+    else NBD_BWD(true, false, false, causal_order(bwd_kernel<true, false>));
   } else {
-    if (fd) NBD_BWD(false, true, none);
-    else NBD_BWD(false, false, none);
+    if (fd) NBD_BWD(false, true, false, none);
+    else NBD_BWD(false, false, false, none);
   }
 #undef NBD_BWD
   C10_HIP_KERNEL_LAUNCH_CHECK();
@@ -995,10 +1118,28 @@ void attn_bwd_hip(const at::Tensor& dout, const at::Tensor& q, const at::Tensor&
   }
 }
 
+void attn_bwd_hip(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                  const at::Tensor& out, const at::Tensor& lse, bool causal, double scale, const at::Tensor& dq,
+                  const at::Tensor& dk, const at::Tensor& dv, const c10::optional<at::Tensor>& rope_cos,
+                  const c10::optional<at::Tensor>& rope_sin, const c10::optional<at::Tensor>& delta_in) {
+  bwd_impl(dout, q, k, v, out, lse, causal, scale, dq, dk, dv, rope_cos, rope_sin, delta_in, nullptr, nullptr);
+}
+
+void attn_bwd_packed_hip(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                         const at::Tensor& out, const at::Tensor& lse, double scale, at::Tensor dq, at::Tensor dk,
+                         at::Tensor dv, const c10::optional<at::Tensor>& rope_cos,
+                         const c10::optional<at::Tensor>& rope_sin, const at::Tensor& kstart, const at::Tensor& qend) {
+  TORCH_CHECK(q.dim() == 4, "attn: q must be [B, H, T, 64]");
+  bwd_impl(dout, q, k, v, out, lse, true, scale, dq, dk, dv, rope_cos, rope_sin, c10::nullopt,
+           bound_of(kstart, q, "kstart"), bound_of(qend, q, "qend"));
+}
+
 }  // namespace attn
 }  // namespace nbd
 
 TORCH_LIBRARY_IMPL(nbd, CUDA, m) {
   m.impl("attn_fwd", &nbd::attn::attn_fwd_hip);
   m.impl("attn_bwd", &nbd::attn::attn_bwd_hip);
+  m.impl("attn_fwd_packed", &nbd::attn::attn_fwd_packed_hip);
+  m.impl("attn_bwd_packed", &nbd::attn::attn_bwd_packed_hip);
 }

@@ -14,6 +14,13 @@ TORCH_LIBRARY(nbd, m) {
   m.def("attn_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor out, Tensor lse, bool causal, float scale, "
         "Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor? rope_cos=None, Tensor? rope_sin=None, "
         "Tensor? delta=None) -> ()");
+  // packed rows (several documents per row, csrc/kernels/packed.hip + the SEG kernels of attn.hip): causal only
+  m.def("packed_bounds(Tensor position_ids, Tensor(a!) bad) -> (Tensor kstart, Tensor qend)");
+  m.def("attn_fwd_packed(Tensor q, Tensor k, Tensor v, float scale, Tensor? rope_cos, Tensor? rope_sin, "
+        "Tensor kstart) -> (Tensor, Tensor)");
+  m.def("attn_bwd_packed(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor out, Tensor lse, float scale, "
+        "Tensor(a!) dq, Tensor(b!) dk, Tensor(c!) dv, Tensor? rope_cos, Tensor? rope_sin, Tensor kstart, "
+        "Tensor qend) -> ()");
   m.def("decode_attn(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor pos, int n_head, float scale, "
         "int kv_len_max, Tensor? rope_cos, Tensor? rope_sin, Tensor(c!) partials) -> Tensor");
   m.def("greedy_advance(Tensor logits, Tensor(a!) tok, Tensor(b!) pos, Tensor(c!) out, Tensor(d!)? done, int eos) -> ()");

@@ -25,6 +25,10 @@ HF semantics kept by the one-line swap (``native()``):
   without a host sync, so the reported batch has already been applied — ``NBD_MASK_CHECK_SYNC=1``
   raises on the offending call instead; inside a ``GraphedStep`` the check follows the replays).
   The causal LM needs right padding (reported the same way).
+* ``position_ids`` (causal LM and ``LlamaModel`` only): rows packed with several documents, positions
+  restarting at 0 per document (``transformers.DataCollatorWithFlattening``, ``data.pack_sequences``)
+  — document-masked flash attention (``ops.packed_bounds`` + ``ops.attention_qkv(bounds=)``), the
+  stack op by op; see ``LlamaModel.forward`` for what it does not cover.
 * forward (pre-)hooks and backward hooks on the decoder layers or any of their submodules (or
   global module hooks): the model then runs module by module, HF's structure — each layer is
   called as ``layer(hidden_states, ...)`` and returns the residual stream, attention honours the
@@ -212,15 +216,20 @@ class LlamaAttention(nn.Module):
         self.o_proj = nn.Linear(self.H * self.D, c.hidden_size, bias=c.o_bias)
         self.window = c.sliding_window
 
-    def forward(self, x, cos, sin, kv=None, key_mask=None):
+    def forward(self, x, cos, sin, kv=None, key_mask=None, bounds=None):
+        """``bounds`` (``ops.PackedBounds``): packed rows — causal attention inside each document."""
         if self.window is not None and x.shape[1] > self.window:
             raise NotImplementedError(f"sliding-window attention: {x.shape[1]} positions > window {self.window}")
+        if bounds is not None and (kv is not None or key_mask is not None):
+            raise ValueError("LlamaAttention: bounds (packed rows) go with neither a KV cache nor a key mask")
         # RoPE is applied inside the attention kernels on the HIP path (rope_ + SDPA otherwise)
         qkv = ops.gemm_linear(x, self.qkv_proj.weight, self.qkv_proj.bias)  # HIP MFMA GEMM on GPU bf16
         if kv is not None:  # (KVCache, layer): generation prefill, before anything rotates qkv in place
             kv[0].store(kv[1], qkv, rope=(cos, sin))
         if key_mask is not None:
             a = _masked_attention(qkv, self.H, self.Hkv, cos, sin, key_mask)
+        elif bounds is not None:
+            a = ops.attention_qkv(qkv, self.H, causal=True, n_kv_head=self.Hkv, rope=(cos, sin), bounds=bounds)
         else:
             a = ops.attention_qkv(qkv, self.H, causal=True, n_kv_head=self.Hkv, rope=(cos, sin))
         return ops.gemm_linear(a, self.o_proj.weight, self.o_proj.bias)
@@ -256,10 +265,12 @@ class LlamaDecoderLayer(nn.Module):
         self.post_attention_layernorm = RMSNorm(c.hidden_size, c.rms_norm_eps)
         self.mlp = LlamaMLP(c)
 
-    def forward(self, hidden_states, cos, sin, key_mask=None):
+    def forward(self, hidden_states, cos, sin, key_mask=None, bounds=None):
         """HF ``LlamaDecoderLayer.forward``'s structure (the module path, taken when hooks are
         registered): residual stream in, residual stream out, every submodule called as a module."""
         kw = {} if key_mask is None else {"key_mask": key_mask}
+        if bounds is not None:
+            kw["bounds"] = bounds
         x = hidden_states + self.self_attn(self.input_layernorm(hidden_states), cos, sin, **kw)
         return x + self.mlp(self.post_attention_layernorm(x))
 
@@ -345,6 +356,23 @@ class _MaskCheck:
         self.ev.record()
 
 
+class _PackedCheck(_MaskCheck):
+    """The same lazy flag for ``position_ids`` (``ops.packed_bounds``): a row that is not
+    consecutive inside a document was still attended document by document as its zeros delimit
+    them — reported one call late (``NBD_MASK_CHECK_SYNC=1``: on the offending call)."""
+
+    def _raise(self, what: str, late: bool) -> None:
+        self.dev.zero_()
+        when = ("It was seen in an EARLIER call, whose batch has already been applied (documents delimited by the "
+                "zeros of position_ids); NBD_MASK_CHECK_SYNC=1 raises on the offending call instead"
+                if late else "nothing of this batch was applied")
+        raise ValueError(f"nbd Llama: position_ids {what}.  {when}")
+
+
+_PACKED_WHAT = ("must count 0, 1, 2, ... inside each document of a packed row (a document starts where they are 0); "
+                "other position layouts are not supported")
+
+
 class _CapturedMaskCheck:
     """A mask check captured into a HIP graph: the prep kernel (and its flag update) replays with
     the graph, so ``GraphedStep`` arms the flag's copy after each replay and polls it before the
@@ -419,20 +447,54 @@ class LlamaModel(nn.Module):
             self._hook_probe = (key, dicts)
         return any(self._hook_probe[1]) or _global_hooks()
 
-    def forward_modules(self, input_ids, attention_mask=None):
+    def forward_modules(self, input_ids, attention_mask=None, bounds=None):
         """Module-by-module forward in HF's structure (hooks fire; ``attention_mask`` masks keys
-        exactly as HF does).  Parameters compute in their own dtype."""
+        exactly as HF does; ``bounds``: packed rows).  Parameters compute in their own dtype."""
         T = input_ids.shape[1]
         cos, sin = self.rope(T, input_ids.device)
         key_mask = None if attention_mask is None else attention_mask != 0
         x = self.embed_tokens(input_ids)
         for layer in self.layers:
-            x = layer(x, cos, sin, key_mask) if key_mask is not None else layer(x, cos, sin)
+            if bounds is not None:
+                x = layer(x, cos, sin, bounds=bounds)
+            else:
+                x = layer(x, cos, sin, key_mask) if key_mask is not None else layer(x, cos, sin)
         return self.norm(x)
 
-    def forward(self, input_ids, cache=None, attention_mask=None):
+    def packed_bounds(self, input_ids, position_ids, attention_mask=None, cache=None):
+        """The documents of packed rows from ``position_ids`` (one launch, ``ops.packed_bounds``);
+        a row that does not count up inside a document is reported by the lazy flag."""
+        if attention_mask is not None:
+            raise ValueError("nbd Llama: position_ids (packed rows) and attention_mask are exclusive: with packed rows "
+                             "a padded tail is simply one more document (its labels -100)")
+        if cache is not None:
+            raise ValueError("nbd Llama: position_ids (packed rows) are for training; generation takes none")
+        if tuple(position_ids.shape) != tuple(input_ids.shape):
+            raise ValueError(f"nbd Llama: position_ids {tuple(position_ids.shape)} must match input_ids "
+                             f"{tuple(input_ids.shape)}")
+        chk = self.__dict__.setdefault("_packed_check", _PackedCheck())
+        chk.poll(1, _PACKED_WHAT)
+        bounds = ops.packed_bounds(position_ids.to(input_ids.device), chk.flag(input_ids.device))
+        chk.arm(1, _PACKED_WHAT)
+        return bounds
+
+    def forward(self, input_ids, cache=None, attention_mask=None, position_ids=None):
         """``cache`` (a ``generation.KVCache``) receives every layer's rotated k and v.
-        ``attention_mask`` given, or hooks registered: the module path (``forward_modules``)."""
+        ``attention_mask`` given, or hooks registered: the module path (``forward_modules``).
+
+        ``position_ids`` [B, T] (restarting at 0 where a document starts, as
+        ``transformers.DataCollatorWithFlattening`` emits): packed rows — every token attends
+        causally inside its own document.  The bounds are computed once and shared by all layers;
+        the stack runs op by op (``LlamaAttention.forward(..., bounds=)``, ``ops.add_rms_norm``,
+        ``LlamaMLP``) with the parameters as stored (no ``compute_dtype`` cast), or module by module
+        with hooks registered.  RoPE still rotates by the row index: scores depend on position
+        differences only, so that is exact inside a document.  ``attention_mask`` together with
+        ``position_ids`` raises ``ValueError`` (a padded tail is simply one more document).  Not
+        covered: the fused per-block node ``llama_block_ag`` and the block / stack graphs, the
+        tensor- and context-parallel attention classes (``TypeError``), GPT-2 (learned positions),
+        ``LlamaForSequenceClassification`` and generation."""
+        if position_ids is not None:
+            return self._forward_packed(input_ids, self.packed_bounds(input_ids, position_ids, attention_mask, cache))
         if cache is None and (attention_mask is not None or self.hooked()):
             return self.forward_modules(input_ids, attention_mask)
         c = self.config
@@ -467,6 +529,22 @@ class LlamaModel(nn.Module):
             # per-block graphs: the last block's output is its graph's static memory — the model's
             # output is the caller's to keep
             h = h.clone()
+        return h
+
+    def _forward_packed(self, input_ids, bounds):
+        """Packed rows: the op-by-op route with one set of bounds for every layer (module by
+        module with hooks registered); parameters run as stored."""
+        if self.hooked():
+            return self.forward_modules(input_ids, bounds=bounds)
+        c = self.config
+        cos, sin = self.rope(input_ids.shape[1], input_ids.device)
+        ln0 = self.layers[0].input_layernorm
+        x, h = ops.embed_rms_norm(input_ids, self.embed_tokens.weight, ln0.weight, ln0.eps)
+        for i, layer in enumerate(self.layers):
+            nxt = self.layers[i + 1].input_layernorm if i + 1 < len(self.layers) else self.norm
+            a = layer.self_attn(h, cos, sin, bounds=bounds)
+            x, h = ops.add_rms_norm(x, a, layer.post_attention_layernorm.weight, c.rms_norm_eps)
+            x, h = ops.add_rms_norm(x, layer.mlp(h), nxt.weight, c.rms_norm_eps)
         return h
 
     def _graph_mode(self) -> int:
@@ -617,15 +695,25 @@ class LlamaForCausalLM(_LlamaPreTrained):
         if c.tie_word_embeddings:
             self.lm_head.weight = self.model.embed_tokens.weight
 
-    def forward(self, input_ids, labels=None, return_logits: bool = True, attention_mask=None):
+    def forward(self, input_ids, labels=None, return_logits: bool = True, attention_mask=None, position_ids=None):
         """Next-token loss of ``labels`` (shifted here: ``logits[:, t]`` predicts ``labels[:, t+1]``).
         Under context parallelism (``parallel.context.parallelize_llama_context``) the shard's
         ``labels`` must come already shifted on the full sequence (``context.shift_labels``) and
         the loss is this rank's ``context_loss`` share of the group-wide token mean.
         ``attention_mask``: right padding on the fused path (real tokens' logits and the loss
         over them equal HF's; anything else is reported at the next call); with hooks registered
-        any mask, exactly (the module path)."""
-        if self.model.hooked():
+        any mask, exactly (the module path).
+        ``position_ids``: packed rows (``LlamaModel.forward``; ``data.pack_sequences`` or
+        ``transformers.DataCollatorWithFlattening`` build them).  A target whose position is 0 — the
+        first token of a document — is ignored (set to -100 here, idempotent with collators that
+        already do), so no document predicts the next one's first token.  Exclusive with
+        ``attention_mask`` (``ValueError``); not under context / tensor parallelism, not in
+        generation."""
+        if position_ids is not None:
+            h = self.model(input_ids, attention_mask=attention_mask, position_ids=position_ids)
+            if labels is not None:
+                labels = labels.masked_fill(position_ids.to(labels.device) == 0, -100)
+        elif self.model.hooked():
             h = self.model.forward_modules(input_ids, attention_mask)
         else:
             if attention_mask is not None:

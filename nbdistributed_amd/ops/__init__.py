@@ -29,6 +29,9 @@ decode_attention (K13) one-token attention over a KV cache: RoPE +      decode.h
                        cache append + softmax·V + chunk merge           merge kernel)
 linear_small (K14)     decode linear: LN/RMS prologue + x·Wᵀ (MFMA) +   smallm.hip
                        bias / GELU / SwiGLU / residual epilogue, M ≤ 64
+packed_bounds (K16)    position_ids of packed rows -> per-query start /  packed.hip (one wave per
+                       per-key end of the document, for the document-    row); attn.hip SEG kernels
+                       masked K7 kernels (attention_qkv(bounds=))
 =====================  ==============================================  =========================
 
 GPU tensors always go to the HIP kernels; if ``libnbd_ops.so`` cannot be loaded on a GPU box the
@@ -39,7 +42,7 @@ from __future__ import annotations
 
 from . import _lib
 from ._lib import _require, load_library, native_available
-from .attention import attention_qkv, flash_attention, flash_supported
+from .attention import PackedBounds, attention_qkv, flash_attention, flash_supported, packed_bounds
 from . import graddst
 from .bucket import (_ref_flatten, _ref_prereduce, _ref_unflatten, bucket_flatten, bucket_unflatten, local_prereduce,
                      plan_offsets, prereduce_into_bucket)
@@ -66,4 +69,4 @@ __all__ = ["linear_tiny", "bucket_flatten", "bucket_unflatten", "local_prereduce
            "flash_attention", "attention_qkv", "decode_attention", "decode_attention_reference", "linear_small", "linear_small_reference", "flash_supported", "layer_norm", "add_layer_norm", "linear",
            "colsum", "embedding", "embedding_tok_pos", "gemm_linear", "llama_block", "block_graphs", "block_graphs_memory", "block_graphs_reset", "block_graphs_stats", "cast_buffers_memory", "mlp_gelu", "mlp_swiglu", "rms_norm", "add_rms_norm", "embed_rms_norm", "tokpos_layer_norm", "rope_", "rope_tables", "swiglu", "tensor_summary",
            "tensor_summary_text", "tensor_summary_raw", "plan_offsets", "native_available", "load_library",
-           "SUMMARY_FIELDS", "seqcls_prep"]
+           "SUMMARY_FIELDS", "seqcls_prep", "packed_bounds", "PackedBounds"]

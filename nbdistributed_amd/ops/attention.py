@@ -75,8 +75,93 @@ def _attn_fns():
             torch.ops.nbd.attn_bwd(do, q, k, v, o, lse, ctx.causal, ctx.scale, dq, dk, dv, cos, sin)
             return dqkv, None, None, None, None, None, None
 
-    _AttnFns = (_FlashAttention, _FlashAttentionQKV)
+    class _FlashAttentionQKVPacked(torch.autograd.Function):
+        """``_FlashAttentionQKV`` for packed rows: causal inside each document of ``PackedBounds``
+        (``nbd::attn_fwd_packed`` / ``attn_bwd_packed``); the packed gradient is written directly."""
+
+        @staticmethod
+        def forward(ctx, qkv, n_head, n_kv, scale, cos, sin, kstart, qend):
+            B, T, _ = qkv.shape
+            q, k, v = _split(qkv, n_head, n_kv)
+            o, lse = torch.ops.nbd.attn_fwd_packed(q, k, v, scale, cos, sin, kstart)
+            ctx.save_for_backward(qkv, o, lse)
+            ctx.n_head, ctx.n_kv, ctx.scale = n_head, n_kv, scale
+            ctx.consts = (cos, sin, kstart, qend)  # constant tables (no gradient), kept by reference
+            return o.transpose(1, 2).reshape(B, T, -1)
+
+        @staticmethod
+        def backward(ctx, dy):
+            qkv, o, lse = ctx.saved_tensors
+            cos, sin, kstart, qend = ctx.consts
+            B, T, _ = qkv.shape
+            q, k, v = _split(qkv, ctx.n_head, ctx.n_kv)
+            dy = dy if dy.is_contiguous() else dy.contiguous()
+            dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
+            dq, dk, dv = _split(dqkv, ctx.n_head, ctx.n_kv)
+            do = dy.view(B, T, ctx.n_head, -1).transpose(1, 2)
+            torch.ops.nbd.attn_bwd_packed(do, q, k, v, o, lse, ctx.scale, dq, dk, dv, cos, sin, kstart, qend)
+            return dqkv, None, None, None, None, None, None, None
+
+    _AttnFns = (_FlashAttention, _FlashAttentionQKV, _FlashAttentionQKVPacked)
     return _AttnFns
+
+
+class PackedBounds:
+    """Document bounds of packed rows (several documents back to back in one row), from
+    :func:`packed_bounds`: ``kstart[b, i]`` = start of query ``i``'s document, ``qend[b, j]`` = one
+    past the end of key ``j``'s document, both int32 [B, T] and non-decreasing along the row.
+    Query ``i`` sees key ``j`` iff ``kstart[i] <= j <= i`` (equivalently ``j <= i < qend[j]``)."""
+
+    __slots__ = ("kstart", "qend")
+
+    def __init__(self, kstart, qend):
+        self.kstart, self.qend = kstart, qend
+
+    def allow(self):
+        """The dense boolean mask [B, 1, T, T] (True = visible): the SDPA fallback's."""
+        import torch
+
+        T = self.kstart.shape[1]
+        ar = torch.arange(T, device=self.kstart.device)
+        return ((ar[None, None, :] <= ar[None, :, None]) & (ar[None, None, :] >= self.kstart[:, :, None]))[:, None]
+
+
+def _ref_packed_bounds(position_ids, bad=None) -> PackedBounds:
+    """PyTorch reference of ``nbd::packed_bounds`` (CPU; the GPU tests compare the kernel against it)."""
+    import torch
+
+    B, T = position_ids.shape
+    dev = position_ids.device
+    ar = torch.arange(T, device=dev).expand(B, T)
+    start = position_ids == 0
+    start[:, :1] = True
+    kstart = torch.where(start, ar, -1).cummax(1).values
+    nxt = torch.where(start & (ar > 0), ar, T).flip(1).cummin(1).values.flip(1)  # first start at or after t
+    qend = torch.cat([nxt[:, 1:], torch.full((B, 1), T, dtype=nxt.dtype, device=dev)], 1)
+    if bad is not None and T > 1:
+        broken = ((position_ids[:, 1:] != position_ids[:, :-1] + 1) & (position_ids[:, 1:] != 0)).any()
+        bad |= broken.to(bad.dtype).view(1)
+    return PackedBounds(kstart.to(torch.int32), qend.to(torch.int32))
+
+
+def packed_bounds(position_ids, bad=None) -> PackedBounds:
+    """Bounds of the documents packed into each row of ``position_ids`` [B, T] (restarting at 0
+    where a document starts, as ``transformers.DataCollatorWithFlattening`` emits; a document also
+    starts at ``t == 0``).  ``bad`` (int32 [1] on the same device) gets 1 OR-ed in when a row is
+    not consecutive inside a document — read lazily by the caller, never synchronised here.  One
+    HIP launch on the GPU (``csrc/kernels/packed.hip``), torch ops on the CPU."""
+    import torch
+
+    if position_ids.dim() != 2:
+        raise ValueError(f"packed_bounds: position_ids must be [B, T], got {tuple(position_ids.shape)}")
+    if position_ids.is_cuda:
+        _require()
+        if bad is None:
+            bad = torch.zeros(1, dtype=torch.int32, device=position_ids.device)
+        pos = position_ids if position_ids.dtype == torch.int64 and position_ids.is_contiguous() else \
+            position_ids.to(torch.int64).contiguous()
+        return PackedBounds(*torch.ops.nbd.packed_bounds(pos, bad))
+    return _ref_packed_bounds(position_ids.to(torch.int64), bad)
 
 def flash_supported(q) -> bool:
     """The HIP kernels cover bf16, head dim 64, T a multiple of 128 (GPT-2's shapes)."""
@@ -99,11 +184,14 @@ def flash_attention(q, k, v, causal: bool = False, scale: Optional[float] = None
     return F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=sc, enable_gqa=gqa)
 
 def attention_qkv(qkv, n_head: int, causal: bool = True, scale: Optional[float] = None,
-                  n_kv_head: Optional[int] = None, rope=None):
+                  n_kv_head: Optional[int] = None, rope=None, bounds: Optional[PackedBounds] = None):
     """Multi-head attention straight from a packed [B, T, (H + 2·Hkv)·D] projection (GPT-2's
     ``c_attn`` output, or a fused Llama q|k|v projection) to [B, T, H·D].  ``n_kv_head`` < ``n_head``
     is grouped-query attention.  ``rope=(cos, sin)`` (tables from ``rope_tables``) applies rotary
-    embeddings to q and k — inside the attention kernels on the HIP path."""
+    embeddings to q and k — inside the attention kernels on the HIP path.  ``bounds``
+    (:func:`packed_bounds`): rows hold several documents, attention is causal inside each — the
+    document-masked HIP kernels under the same conditions, else SDPA with the dense mask.  RoPE
+    rotates by the row index either way: scores depend on position differences only."""
     import torch
     import torch.nn.functional as F
 
@@ -111,11 +199,18 @@ def attention_qkv(qkv, n_head: int, causal: bool = True, scale: Optional[float] 
     Hkv = n_kv_head or n_head
     D = W // (n_head + 2 * Hkv)
     sc = float(scale) if scale is not None else D ** -0.5
+    if bounds is not None:
+        if not causal:
+            raise ValueError("attention_qkv: bounds (packed rows) need causal=True")
+        if tuple(bounds.kstart.shape) != (B, T):
+            raise ValueError(f"attention_qkv: bounds are for {tuple(bounds.kstart.shape)}, qkv is {(B, T)}")
     if (qkv.is_cuda and qkv.dtype == torch.bfloat16 and D == 64 and T % 128 == 0 and qkv.stride(-1) == 1
             and qkv.stride(1) % 8 == 0 and qkv.stride(0) % 8 == 0 and qkv.data_ptr() % 16 == 0
             and n_head % Hkv == 0):
         _require()
         cos, sin = rope if rope is not None else (None, None)
+        if bounds is not None:
+            return _attn_fns()[2].apply(qkv, int(n_head), int(Hkv), sc, cos, sin, bounds.kstart, bounds.qend)
         from .gemm import _native
 
         if _native():  # the C++ autograd node (csrc/kernels/autograd.hip)
@@ -128,5 +223,8 @@ def attention_qkv(qkv, n_head: int, causal: bool = True, scale: Optional[float] 
     q = qkv[:, :, : n_head * D].view(B, T, n_head, D).transpose(1, 2)
     k = qkv[:, :, n_head * D:(n_head + Hkv) * D].view(B, T, Hkv, D).transpose(1, 2)
     v = qkv[:, :, (n_head + Hkv) * D:].view(B, T, Hkv, D).transpose(1, 2)
-    y = F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=sc, enable_gqa=Hkv != n_head)
+    if bounds is not None:
+        y = F.scaled_dot_product_attention(q, k, v, attn_mask=bounds.allow(), scale=sc, enable_gqa=Hkv != n_head)
+    else:
+        y = F.scaled_dot_product_attention(q, k, v, is_causal=causal, scale=sc, enable_gqa=Hkv != n_head)
     return y.transpose(1, 2).reshape(B, T, n_head * D)
