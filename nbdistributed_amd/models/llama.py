@@ -193,19 +193,23 @@ def _masked_attention(qkv, H: int, Hkv: int, cos, sin, key_mask):
     """Causal GQA attention where key ``j`` of row ``b`` is visible only if ``key_mask[b, j]``
     (HF's 4-D mask from ``attention_mask``).  A query with no visible key (a left pad) attends to
     itself — its output feeds nothing a real token reads.  PyTorch SDPA: the module path only."""
+    from ..ops.attention import _split_qkv
     from ..ops.llama import rope_
 
     B, T, W = qkv.shape
     D = W // (H + 2 * Hkv)
-    qkv = rope_(qkv.contiguous().clone(), cos, sin, H + Hkv, D)
-    q = qkv[:, :, : H * D].view(B, T, H, D).transpose(1, 2)
-    k = qkv[:, :, H * D:(H + Hkv) * D].view(B, T, Hkv, D).transpose(1, 2)
-    v = qkv[:, :, (H + Hkv) * D:].view(B, T, Hkv, D).transpose(1, 2)
+    q, k, v = _split_qkv(rope_(qkv.contiguous().clone(), cos, sin, H + Hkv, D), H, Hkv)
     causal = torch.ones(T, T, dtype=torch.bool, device=qkv.device).tril()
     allow = causal[None] & key_mask.bool()[:, None, :]
     allow = allow | torch.eye(T, dtype=torch.bool, device=qkv.device)[None]
     y = F.scaled_dot_product_attention(q, k, v, attn_mask=allow[:, None], scale=D ** -0.5, enable_gqa=Hkv != H)
     return y.transpose(1, 2).reshape(B, T, H * D)
+
+
+def _given(**kw):
+    """The keyword arguments that are not None, to pass on: the tensor- and context-parallel
+    attention classes take no ``key_mask`` / ``bounds`` and answer one with ``TypeError``."""
+    return {k: v for k, v in kw.items() if v is not None}
 
 
 class LlamaAttention(nn.Module):
@@ -228,10 +232,8 @@ class LlamaAttention(nn.Module):
             kv[0].store(kv[1], qkv, rope=(cos, sin))
         if key_mask is not None:
             a = _masked_attention(qkv, self.H, self.Hkv, cos, sin, key_mask)
-        elif bounds is not None:
-            a = ops.attention_qkv(qkv, self.H, causal=True, n_kv_head=self.Hkv, rope=(cos, sin), bounds=bounds)
         else:
-            a = ops.attention_qkv(qkv, self.H, causal=True, n_kv_head=self.Hkv, rope=(cos, sin))
+            a = ops.attention_qkv(qkv, self.H, causal=True, n_kv_head=self.Hkv, rope=(cos, sin), bounds=bounds)
         return ops.gemm_linear(a, self.o_proj.weight, self.o_proj.bias)
 
     def decode(self, x, norm_w, eps, cache, layer: int, pos, rope):
@@ -268,9 +270,7 @@ class LlamaDecoderLayer(nn.Module):
     def forward(self, hidden_states, cos, sin, key_mask=None, bounds=None):
         """HF ``LlamaDecoderLayer.forward``'s structure (the module path, taken when hooks are
         registered): residual stream in, residual stream out, every submodule called as a module."""
-        kw = {} if key_mask is None else {"key_mask": key_mask}
-        if bounds is not None:
-            kw["bounds"] = bounds
+        kw = _given(key_mask=key_mask, bounds=bounds)
         x = hidden_states + self.self_attn(self.input_layernorm(hidden_states), cos, sin, **kw)
         return x + self.mlp(self.post_attention_layernorm(x))
 
@@ -455,10 +455,7 @@ class LlamaModel(nn.Module):
         key_mask = None if attention_mask is None else attention_mask != 0
         x = self.embed_tokens(input_ids)
         for layer in self.layers:
-            if bounds is not None:
-                x = layer(x, cos, sin, bounds=bounds)
-            else:
-                x = layer(x, cos, sin, key_mask) if key_mask is not None else layer(x, cos, sin)
+            x = layer(x, cos, sin, **_given(key_mask=key_mask, bounds=bounds))
         return self.norm(x)
 
     def packed_bounds(self, input_ids, position_ids, attention_mask=None, cache=None):
@@ -493,14 +490,15 @@ class LlamaModel(nn.Module):
         covered: the fused per-block node ``llama_block_ag`` and the block / stack graphs, the
         tensor- and context-parallel attention classes (``TypeError``), GPT-2 (learned positions),
         ``LlamaForSequenceClassification`` and generation."""
+        bounds = None
         if position_ids is not None:
-            return self._forward_packed(input_ids, self.packed_bounds(input_ids, position_ids, attention_mask, cache))
+            bounds = self.packed_bounds(input_ids, position_ids, attention_mask, cache)
         if cache is None and (attention_mask is not None or self.hooked()):
-            return self.forward_modules(input_ids, attention_mask)
+            return self.forward_modules(input_ids, attention_mask, bounds)
         c = self.config
         T = input_ids.shape[1]
         cos, sin = self.rope(T, input_ids.device)
-        cd = self.cast_dtype(input_ids) if cache is None else None
+        cd = self.cast_dtype(input_ids) if cache is None and bounds is None else None
         if cd is not None:
             return self._forward_cast(input_ids, cd, cos, sin)
         # the residual stream: each block's two residual adds are fused with the RMSNorm after them
@@ -510,8 +508,9 @@ class LlamaModel(nn.Module):
         for i, layer in enumerate(self.layers):
             nxt = self.layers[i + 1].input_layernorm if i + 1 < len(self.layers) else self.norm
             at = layer.self_attn
-            # (plain modules only: tensor / context parallelism swap in their own attention / MLP)
-            if (cache is None and type(at) is LlamaAttention and type(layer.mlp) is LlamaMLP
+            # (plain modules only: tensor / context parallelism swap in their own attention / MLP;
+            # the block node knows no bounds)
+            if (cache is None and bounds is None and type(at) is LlamaAttention and type(layer.mlp) is LlamaMLP
                     and (at.window is None or T <= at.window)):
                 # the whole block as one autograd node (GPU bf16; None -> the op-by-op path below)
                 r = ops.llama_block(x, h, at.qkv_proj.weight, at.qkv_proj.bias, at.o_proj.weight, at.o_proj.bias,
@@ -521,30 +520,16 @@ class LlamaModel(nn.Module):
                 if r is not None:
                     x, h = r
                     continue
-            a = layer.self_attn(h, cos, sin) if cache is None else layer.self_attn(h, cos, sin, kv=(cache, i))
+            # (a cache and bounds never come together: packed_bounds() refuses a cache)
+            a = (layer.self_attn(h, cos, sin, **_given(bounds=bounds)) if cache is None
+                 else layer.self_attn(h, cos, sin, kv=(cache, i)))
             x, h = ops.add_rms_norm(x, a, layer.post_attention_layernorm.weight, c.rms_norm_eps)
             m = layer.mlp(h)
             x, h = ops.add_rms_norm(x, m, nxt.weight, c.rms_norm_eps)
-        if h.is_cuda and self._graphs_on():
+        if h.is_cuda and bounds is None and self._graphs_on():
             # per-block graphs: the last block's output is its graph's static memory — the model's
             # output is the caller's to keep
             h = h.clone()
-        return h
-
-    def _forward_packed(self, input_ids, bounds):
-        """Packed rows: the op-by-op route with one set of bounds for every layer (module by
-        module with hooks registered); parameters run as stored."""
-        if self.hooked():
-            return self.forward_modules(input_ids, bounds=bounds)
-        c = self.config
-        cos, sin = self.rope(input_ids.shape[1], input_ids.device)
-        ln0 = self.layers[0].input_layernorm
-        x, h = ops.embed_rms_norm(input_ids, self.embed_tokens.weight, ln0.weight, ln0.eps)
-        for i, layer in enumerate(self.layers):
-            nxt = self.layers[i + 1].input_layernorm if i + 1 < len(self.layers) else self.norm
-            a = layer.self_attn(h, cos, sin, bounds=bounds)
-            x, h = ops.add_rms_norm(x, a, layer.post_attention_layernorm.weight, c.rms_norm_eps)
-            x, h = ops.add_rms_norm(x, layer.mlp(h), nxt.weight, c.rms_norm_eps)
         return h
 
     def _graph_mode(self) -> int:

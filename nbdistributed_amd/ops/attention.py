@@ -8,6 +8,17 @@ from ._lib import _require
 
 _AttnFns = None
 
+
+def _split_qkv(qkv, H: int, Hkv: int):
+    """q, k, v as [B, heads, T, D] views of a packed [B, T, (H + 2·Hkv)·D] projection."""
+    B, T, W = qkv.shape
+    D = W // (H + 2 * Hkv)
+    q = qkv[:, :, : H * D].view(B, T, H, D).transpose(1, 2)
+    k = qkv[:, :, H * D:(H + Hkv) * D].view(B, T, Hkv, D).transpose(1, 2)
+    v = qkv[:, :, (H + Hkv) * D:].view(B, T, Hkv, D).transpose(1, 2)
+    return q, k, v
+
+
 def _attn_fns():
     global _AttnFns
     if _AttnFns is not None:
@@ -40,69 +51,42 @@ def _attn_fns():
             torch.ops.nbd.attn_bwd(_fix(do), q, k, v, o, lse, ctx.causal, ctx.scale, dq, dk, dv, None, None)
             return dq, dk, dv, None, None
 
-    def _split(qkv, H, Hkv):
-        B, T, W = qkv.shape
-        D = W // (H + 2 * Hkv)
-        q = qkv[:, :, : H * D].view(B, T, H, D).transpose(1, 2)
-        k = qkv[:, :, H * D:(H + Hkv) * D].view(B, T, Hkv, D).transpose(1, 2)
-        v = qkv[:, :, (H + Hkv) * D:].view(B, T, Hkv, D).transpose(1, 2)
-        return q, k, v
-
     class _FlashAttentionQKV(torch.autograd.Function):
         """[B, T, (H + 2·Hkv)·D] packed projection in, [B, T, H·D] out; the backward writes the
-        packed gradient directly (no split/cat, no transposes).  Hkv < H: grouped-query attention."""
+        packed gradient directly (no split/cat, no transposes).  Hkv < H: grouped-query attention.
+        ``kstart`` / ``qend`` (``PackedBounds``; both or neither): packed rows, causal inside each
+        document (``nbd::attn_fwd_packed`` / ``attn_bwd_packed``)."""
 
         @staticmethod
-        def forward(ctx, qkv, n_head, n_kv, causal, scale, cos, sin):
+        def forward(ctx, qkv, n_head, n_kv, causal, scale, cos, sin, kstart=None, qend=None):
             B, T, _ = qkv.shape
-            q, k, v = _split(qkv, n_head, n_kv)
-            o, lse = torch.ops.nbd.attn_fwd(q, k, v, causal, scale, cos, sin)
+            q, k, v = _split_qkv(qkv, n_head, n_kv)
+            if kstart is not None:
+                o, lse = torch.ops.nbd.attn_fwd_packed(q, k, v, scale, cos, sin, kstart)
+            else:
+                o, lse = torch.ops.nbd.attn_fwd(q, k, v, causal, scale, cos, sin)
             ctx.save_for_backward(qkv, o, lse)
             ctx.n_head, ctx.n_kv, ctx.causal, ctx.scale = n_head, n_kv, causal, scale
-            ctx.rope = (cos, sin)  # constant tables (no gradient), kept by reference
-            return o.transpose(1, 2).reshape(B, T, -1)  # o is stored [B, T, H, D]: a view
-
-        @staticmethod
-        def backward(ctx, dy):
-            qkv, o, lse = ctx.saved_tensors
-            cos, sin = ctx.rope
-            B, T, _ = qkv.shape
-            q, k, v = _split(qkv, ctx.n_head, ctx.n_kv)
-            dy = dy if dy.is_contiguous() else dy.contiguous()
-            dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
-            dq, dk, dv = _split(dqkv, ctx.n_head, ctx.n_kv)
-            do = dy.view(B, T, ctx.n_head, -1).transpose(1, 2)
-            torch.ops.nbd.attn_bwd(do, q, k, v, o, lse, ctx.causal, ctx.scale, dq, dk, dv, cos, sin)
-            return dqkv, None, None, None, None, None, None
-
-    class _FlashAttentionQKVPacked(torch.autograd.Function):
-        """``_FlashAttentionQKV`` for packed rows: causal inside each document of ``PackedBounds``
-        (``nbd::attn_fwd_packed`` / ``attn_bwd_packed``); the packed gradient is written directly."""
-
-        @staticmethod
-        def forward(ctx, qkv, n_head, n_kv, scale, cos, sin, kstart, qend):
-            B, T, _ = qkv.shape
-            q, k, v = _split(qkv, n_head, n_kv)
-            o, lse = torch.ops.nbd.attn_fwd_packed(q, k, v, scale, cos, sin, kstart)
-            ctx.save_for_backward(qkv, o, lse)
-            ctx.n_head, ctx.n_kv, ctx.scale = n_head, n_kv, scale
             ctx.consts = (cos, sin, kstart, qend)  # constant tables (no gradient), kept by reference
-            return o.transpose(1, 2).reshape(B, T, -1)
+            return o.transpose(1, 2).reshape(B, T, -1)  # o is stored [B, T, H, D]: a view
 
         @staticmethod
         def backward(ctx, dy):
             qkv, o, lse = ctx.saved_tensors
             cos, sin, kstart, qend = ctx.consts
             B, T, _ = qkv.shape
-            q, k, v = _split(qkv, ctx.n_head, ctx.n_kv)
+            q, k, v = _split_qkv(qkv, ctx.n_head, ctx.n_kv)
             dy = dy if dy.is_contiguous() else dy.contiguous()
             dqkv = torch.empty_like(qkv, memory_format=torch.contiguous_format)
-            dq, dk, dv = _split(dqkv, ctx.n_head, ctx.n_kv)
+            dq, dk, dv = _split_qkv(dqkv, ctx.n_head, ctx.n_kv)
             do = dy.view(B, T, ctx.n_head, -1).transpose(1, 2)
-            torch.ops.nbd.attn_bwd_packed(do, q, k, v, o, lse, ctx.scale, dq, dk, dv, cos, sin, kstart, qend)
-            return dqkv, None, None, None, None, None, None, None
+            if kstart is not None:
+                torch.ops.nbd.attn_bwd_packed(do, q, k, v, o, lse, ctx.scale, dq, dk, dv, cos, sin, kstart, qend)
+            else:
+                torch.ops.nbd.attn_bwd(do, q, k, v, o, lse, ctx.causal, ctx.scale, dq, dk, dv, cos, sin)
+            return dqkv, None, None, None, None, None, None, None, None
 
-    _AttnFns = (_FlashAttention, _FlashAttentionQKV, _FlashAttentionQKVPacked)
+    _AttnFns = (_FlashAttention, _FlashAttentionQKV)
     return _AttnFns
 
 
@@ -209,20 +193,17 @@ def attention_qkv(qkv, n_head: int, causal: bool = True, scale: Optional[float] 
             and n_head % Hkv == 0):
         _require()
         cos, sin = rope if rope is not None else (None, None)
-        if bounds is not None:
-            return _attn_fns()[2].apply(qkv, int(n_head), int(Hkv), sc, cos, sin, bounds.kstart, bounds.qend)
         from .gemm import _native
 
-        if _native():  # the C++ autograd node (csrc/kernels/autograd.hip)
+        if bounds is None and _native():  # the C++ autograd node (csrc/kernels/autograd.hip)
             return torch.ops.nbd.attn_qkv_ag(qkv, int(n_head), int(Hkv), bool(causal), sc, cos, sin)
-        return _attn_fns()[1].apply(qkv, int(n_head), int(Hkv), bool(causal), sc, cos, sin)
+        kq = (bounds.kstart, bounds.qend) if bounds is not None else ()
+        return _attn_fns()[1].apply(qkv, int(n_head), int(Hkv), bool(causal), sc, cos, sin, *kq)
     if rope is not None:
         from .llama import rope_
 
         qkv = rope_(qkv if qkv.is_contiguous() else qkv.contiguous(), rope[0], rope[1], n_head + Hkv, D)
-    q = qkv[:, :, : n_head * D].view(B, T, n_head, D).transpose(1, 2)
-    k = qkv[:, :, n_head * D:(n_head + Hkv) * D].view(B, T, Hkv, D).transpose(1, 2)
-    v = qkv[:, :, (n_head + Hkv) * D:].view(B, T, Hkv, D).transpose(1, 2)
+    q, k, v = _split_qkv(qkv, n_head, Hkv)
     if bounds is not None:
         y = F.scaled_dot_product_attention(q, k, v, attn_mask=bounds.allow(), scale=sc, enable_gqa=Hkv != n_head)
     else:
