@@ -4,6 +4,14 @@
 the same weights; plus the decode-attention kernel alone (achieved HBM bandwidth over the cache).
 
     python benchmarks/generate_bench.py [--batches 1,8,32] [--prompt 128] [--new 256]
+
+``--continue``: the time to the first token of a second turn, continuing from the returned cache
+(``generate(turn, 1, cache=cache)``: block append, ``csrc/kernels/append.hip``) against the only
+way without it, re-prefilling the whole history (``generate(history + turn, 1)``); SmolLM2-135M
+and GPT-2-small shapes, rounds of the two interleaved.
+
+    python benchmarks/generate_bench.py --continue [--models smollm2,gpt2] [--batches 1,8]
+        [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -60,8 +68,73 @@ def kernel_bench(rows):
     return out
 
 
+def continue_bench(a):
+    import statistics
+
+    from nbdistributed_amd.generation import generate
+    from nbdistributed_amd.models import GPT2, GPT2Config, SMOLLM2_135M
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+
+    hists = [int(x) for x in a.hist.split(",")]
+    turns = [int(x) for x in a.turn.split(",")]
+    room = max(hists) + max(turns) + 2
+    res = {"what": "ms to the first token of turn 2: continue from the cache vs re-prefill of history + turn",
+           "dtype": "bf16", "rounds": a.rounds, "points": []}
+    for name in a.models.split(","):
+        torch.manual_seed(0)
+        if name == "smollm2":
+            cfg = {k: v for k, v in SMOLLM2_135M.items() if k != "hidden_act"}
+            m, vocab = LlamaForCausalLM(LlamaConfig(**cfg)), cfg["vocab_size"]
+        else:  # GPT-2 small's shapes with a position table long enough for the histories
+            m, vocab = GPT2(GPT2Config(n_positions=-(-room // 128) * 128 + 128)), 50257
+        m = m.to("cuda", torch.bfloat16).eval()
+        for B in [int(x) for x in a.batches.split(",")]:
+            for hist in hists:
+                # turn 1 leaves hist - 1 rows in the cache and one pending token: a history of hist tokens
+                ids = torch.randint(1, vocab, (B, hist - 8), device="cuda")
+                out1, cache = generate(m, ids, 8, t_max=-(-(hist + max(turns) + 2) // 128) * 128, graph=False,
+                                       return_cache=True)
+                len0, pend0 = cache.lengths.clone(), cache.pending.clone()
+                for turn in turns:
+                    new = torch.randint(1, vocab, (B, turn), device="cuda")
+                    whole = torch.cat([out1, new], 1)
+
+                    def cont():
+                        cache.lengths, cache.pending = len0.clone(), pend0.clone()
+                        return generate(m, new, 1, cache=cache, graph=False)
+
+                    def full():
+                        return generate(m, whole, 1, graph=False)
+
+                    same = bool((cont()[:, -1] == full()[:, -1]).all())  # (also the warm-up of both)
+                    tc, tf = [], []
+                    for _ in range(a.rounds):  # interleaved: drift hits both arms alike
+                        for fn, ts in ((cont, tc), (full, tf)):
+                            torch.cuda.synchronize()
+                            t = time.perf_counter()
+                            fn()
+                            torch.cuda.synchronize()
+                            ts.append((time.perf_counter() - t) * 1e3)
+                    row = dict(model=name, batch=B, history=hist, turn=turn,
+                               continue_ms=round(statistics.median(tc), 3), continue_min_ms=round(min(tc), 3),
+                               reprefill_ms=round(statistics.median(tf), 3), reprefill_min_ms=round(min(tf), 3),
+                               first_token_same=same)
+                    row["speedup"] = round(row["reprefill_ms"] / row["continue_ms"], 2)
+                    print(json.dumps(row), flush=True)
+                    res["points"].append(row)
+                del cache
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--continue", dest="cont", action="store_true", help="the multi-turn arm (see the module docstring)")
+    ap.add_argument("--models", default="smollm2,gpt2")
+    ap.add_argument("--hist", default="512,2048,4096")
+    ap.add_argument("--turn", default="1,32,128")
+    ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--batches", default="1,8,32")
     ap.add_argument("--prompt", type=int, default=128)
     ap.add_argument("--new", type=int, default=256)
@@ -73,6 +146,10 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.cont:
+        if a.batches == "1,8,32":
+            a.batches = "1,8"
+        return continue_bench(a)
     torch.manual_seed(0)
     hf = None
     if a.model == "smollm2":

@@ -23,6 +23,9 @@ TORCH_LIBRARY(nbd, m) {
         "Tensor qend) -> ()");
   m.def("decode_attn(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor pos, int n_head, float scale, "
         "int kv_len_max, Tensor? rope_cos, Tensor? rope_sin, Tensor(c!) partials) -> Tensor");
+  // a block of new tokens per sequence over the cache (csrc/kernels/append.hip): k | v appended at start[b] + i
+  m.def("append_attn(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor start, Tensor nnew, int n_head, "
+        "float scale, int kv_len_max, Tensor? rope_cos, Tensor? rope_sin) -> Tensor");
   m.def("greedy_advance(Tensor logits, Tensor(a!) tok, Tensor(b!) pos, Tensor(c!) out, Tensor(d!)? done, int eos) -> ()");
   m.def("linear_small(Tensor x, Tensor w, Tensor? bias, Tensor? norm_w, Tensor? norm_b, float eps, int norm, "
         "int act, Tensor? residual) -> Tensor");

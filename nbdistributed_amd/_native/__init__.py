@@ -54,8 +54,9 @@ GPU_ARCH = os.environ.get("NBD_GPU_ARCH", "gfx950")
 
 # per-source flags.  attn.hip: no SLP vectorisation — beside MFMAs a packed v_pk_{add,mul}_f32
 # costs more issue cycles than the two scalar ops it replaces (MI355X_MICROARCH.md, per-instruction
-# cycle constants), and the softmax VALU work is what bounds the attention loops.
-EXTRA_HIP_FLAGS = {"attn.hip": ["-fno-slp-vectorize"]}
+# cycle constants), and the softmax VALU work is what bounds the attention loops.  append.hip runs
+# the same forward body.
+EXTRA_HIP_FLAGS = {"attn.hip": ["-fno-slp-vectorize"], "append.hip": ["-fno-slp-vectorize"]}
 
 
 def cache_root() -> Path:

@@ -13,13 +13,21 @@ The reference's notebooks train; after training, a user of an interactive notebo
 * the positions live on the device, so the whole decode step — sampling included (Gumbel-max on
   the device RNG) — is captured once into a HIP graph and replayed per token: no host launch
   cost and no host sync per token (sequences that reach ``eos_token_id`` keep emitting it; the
-  host checks for all-finished every ``sync_every`` tokens).
+  host checks for all-finished every ``sync_every`` tokens);
+* **continue** — ``generate(..., return_cache=True)`` hands back the cache with each sequence's
+  valid rows (``lengths``) and its last emitted token (``pending``: sampled, not yet in the
+  cache); ``generate(turn, n, cache=cache)`` runs only ``[pending, turn…]`` through the stack,
+  with ``ops.append_attention`` (``csrc/kernels/append.hip``) attending the block over the cache
+  at per-sequence offsets and appending it, then enters the same decode loop — no second prefill
+  of the history.
 
-Models opt in by providing ``kv_layout()``, ``prefill(ids, cache, lengths)`` and
-``decode_step(tok, pos, cache)``; see ``models/gpt2.py`` and ``models/llama.py``.
+Models opt in by providing ``kv_layout()``, ``prefill(ids, cache, lengths)``,
+``decode_step(tok, pos, cache)`` and ``extend(ids, cache, start, nnew)``; see ``models/gpt2.py``
+and ``models/llama.py``.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -39,6 +47,9 @@ class KVCache:
 
         self.workspace = torch.empty(partials_numel(batch, n_head, t_max), dtype=torch.float32, device=device)
         self.kv_len_max: Optional[int] = None  # host bound on max(pos) + 1 (None = t_max)
+        # set by every ``generate`` call (None on a fresh cache), both int64 [B] on the device:
+        self.lengths: Optional[torch.Tensor] = None  # valid rows per sequence
+        self.pending: Optional[torch.Tensor] = None  # the last emitted token, not yet in the cache
 
     @classmethod
     def for_model(cls, model, batch: int, t_max: int, device=None, dtype=None) -> "KVCache":
@@ -71,6 +82,15 @@ class KVCache:
 
         return ops.decode_attention(qkv, self.k[layer], self.v[layer], pos, self.n_head, scale=scale, rope=rope,
                                     kv_len_max=self.kv_len_max, workspace=self.workspace)
+
+    def extend(self, layer: int, qkv: torch.Tensor, start: torch.Tensor, nnew: torch.Tensor, rope=None,
+               scale=None) -> torch.Tensor:
+        """Continue: append the ``nnew[b]`` real rows of ``qkv`` [B, Tn, W] at ``start[b]`` and attend
+        each over the cache up to itself (``ops.append_attention``)."""
+        from . import ops
+
+        return ops.append_attention(qkv, self.k[layer], self.v[layer], start, nnew, self.n_head, scale=scale,
+                                    rope=rope, kv_len_max=self.kv_len_max)
 
 
 def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: Optional[int] = None,
@@ -152,8 +172,101 @@ class _DecodeLoop:
             self.step()
 
 
+def _run_decode(loop: _DecodeLoop, n: int, graph: bool, key_bound: int, eos_token_id, sync_every: int) -> None:
+    """``n`` decode steps of ``loop`` (graph-captured first when ``graph``); ``key_bound`` = host
+    bound on max(pos) + 1 at the first step.  Leaves ``cache.lengths`` / ``cache.pending`` set."""
+    cache = loop.cache
+    if graph and n > 0:
+        loop.capture(warmup=min(2, n))
+    try:
+        for i in range(n):
+            if not graph:
+                cache.kv_len_max = key_bound + i  # known on the host: fewer idle workgroups
+            loop()
+            if eos_token_id is not None and (i + 1) % sync_every == 0 and bool(loop.done.all()):
+                break
+    finally:
+        cache.kv_len_max = None  # the bound only held inside this call (a returned cache is reused later)
+    # what a later ``generate(..., cache=cache)`` continues from: rows [0, pos) are in the cache,
+    # ``tok`` (at position pos) is not — also after an early all-eos break
+    cache.lengths, cache.pending = loop.pos.clone(), loop.tok.clone()
+
+
+def _continue(model, input_ids, max_new_tokens: int, cache: KVCache, lengths, sampling: dict, eos_token_id,
+              pad_token_id: int, graph, sync_every: int):
+    """``generate`` from a returned cache: the block ``[cache.pending, turn…]`` per sequence goes
+    through ``model.extend`` at ``start = cache.lengths``, then the decode loop takes over."""
+    if max_new_tokens <= 0:
+        raise ValueError(f"generate: continuing from a cache needs max_new_tokens >= 1, got {max_new_tokens}")
+    if cache.lengths is None or cache.pending is None:
+        raise ValueError("generate: this cache has no lengths (a fresh KVCache): only a cache returned by "
+                         "generate(..., return_cache=True) can be continued")
+    device = cache.k.device
+    B = cache.batch
+    if input_ids is None:
+        input_ids = torch.zeros((B, 0), dtype=torch.int64, device=device)
+    input_ids = input_ids.to(device)
+    if input_ids.dim() != 2 or input_ids.shape[0] != B:
+        raise ValueError(f"generate: input_ids {tuple(input_ids.shape)} do not match the cache's batch {B}")
+    layout = tuple(model.kv_layout())
+    have = (cache.n_layer, cache.n_head, cache.n_kv, cache.head_dim)
+    if layout != have:
+        raise ValueError(f"generate: the cache's layout (layers, heads, kv heads, head dim) {have} is not the "
+                         f"model's {layout}")
+    Tn = input_ids.shape[1]
+    lens = (torch.full((B,), Tn, dtype=torch.int64, device=device) if lengths is None
+            else lengths.to(device=device, dtype=torch.int64))
+    hist = int(cache.lengths.max())  # the one host sync, before any decoding
+    total = hist + 1 + Tn + max_new_tokens  # positions in use after this call (the pending token is one)
+    if total > cache.t_max:
+        raise ValueError(f"generate: continuing needs {total} cache rows ({hist} held + 1 pending + {Tn} new + "
+                         f"{max_new_tokens} to generate), the cache has t_max {cache.t_max}: reserve room with "
+                         f"t_max= on the first call")
+    limit = model.max_positions()
+    if limit is not None and total > limit:
+        raise ValueError(f"generate: continuing reaches {total} positions ({hist} held + 1 pending + {Tn} new + "
+                         f"{max_new_tokens} to generate), model limit {limit}")
+    window = getattr(getattr(model, "config", None), "sliding_window", None)
+    if window is not None and total > window:
+        raise NotImplementedError(f"generate: {total} positions exceed the model's sliding window ({window}); "
+                                  f"sliding-window decoding is not implemented")
+    start = cache.lengths.clone()
+    nnew = lens + 1
+    ar = torch.arange(Tn, device=device)
+    turn = input_ids.masked_fill(ar[None, :] >= lens[:, None], pad_token_id)
+    chunk = torch.cat([cache.pending.view(B, 1).to(turn.dtype), turn], 1)
+    if device.type == "cuda":
+        # B·(Tn + 1) rows onto the GEMM kernels' 64-row grid once, here (padding columns, nnew
+        # unchanged), instead of a pad and a slice around every GEMM of every layer
+        g = 64 // math.gcd(B, 64)
+        extra = (-chunk.shape[1]) % g
+        if extra:
+            chunk = torch.cat([chunk, chunk.new_full((B, extra), pad_token_id)], 1)
+    cache.kv_len_max = hist + 1 + Tn  # host bound on max(start + nnew)
+    try:
+        logits = model.extend(chunk, cache, start, nnew)
+    finally:
+        cache.kv_len_max = None
+    tok = sample(logits, **sampling)
+    pos = start + nnew  # position of `tok`
+    # the decode loop writes a token at column pos of its output: run it on absolute positions, then
+    # read each row back relative to its turn (column j = position start + 1 + j)
+    out_abs = torch.full((B, total), pad_token_id, dtype=turn.dtype, device=device)
+    out_abs.scatter_(1, pos.view(-1, 1), tok.view(-1, 1))
+    done = (tok == eos_token_id) if eos_token_id is not None else torch.zeros(B, dtype=torch.bool, device=device)
+    if graph is None:
+        graph = device.type == "cuda" and sampling["generator"] is None
+    loop = _DecodeLoop(model, cache, tok, pos, out_abs, done, eos_token_id, sampling)
+    _run_decode(loop, max_new_tokens - 1, graph, hist + 1 + Tn + 1, eos_token_id, sync_every)
+    rel = torch.arange(Tn + max_new_tokens, device=device)
+    out = out_abs.gather(1, (start.view(-1, 1) + 1 + rel[None, :]).clamp_(max=total - 1))
+    out[:, :Tn] = torch.where(ar[None, :] < lens[:, None], turn, out[:, :Tn])
+    return out
+
+
 @torch.no_grad()
-def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, lengths: Optional[torch.Tensor] = None,
+def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
+             lengths: Optional[torch.Tensor] = None, cache: Optional[KVCache] = None,
              temperature: float = 0.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
              eos_token_id: Optional[int] = None, pad_token_id: int = 0, graph: Optional[bool] = None,
              t_max: Optional[int] = None, sync_every: int = 32, generator: Optional[torch.Generator] = None,
@@ -164,7 +277,21 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, lengths: Op
 
     ``temperature`` 0 = greedy; ``top_k`` / ``top_p`` restrict sampling.  ``graph`` (default: on
     for a GPU model without an explicit ``generator``) captures the decode step into a HIP graph.
+
+    ``return_cache=True`` returns ``(out, cache)``; ``cache=`` that object continues the same
+    sequences: ``input_ids`` [B, Tn] then holds the next turn only (right-padded, ``lengths`` its
+    token counts; ``None`` or Tn = 0: keep generating), only the new tokens run through the model
+    (``ops.append_attention`` over the cache), and the result [B, Tn + max_new_tokens] is laid out
+    as above relative to this turn.  The cache must have room: reserve it with ``t_max=`` on the
+    first call (history + 1 + Tn + max_new_tokens rows).  ``ValueError`` for a cache that no
+    ``generate`` call filled, a batch or layout mismatch, too little room, or the model's position
+    limit; one host sync (``cache.lengths.max()``).
     """
+    if cache is not None:
+        sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator)
+        out = _continue(model, input_ids, max_new_tokens, cache, lengths, sampling, eos_token_id, pad_token_id,
+                        graph, sync_every)
+        return (out, cache) if return_cache else out
     device = input_ids.device
     B, T0 = input_ids.shape
     if max_new_tokens <= 0:
@@ -203,18 +330,7 @@ def generate(model, input_ids: torch.Tensor, max_new_tokens: int, *, lengths: Op
     if graph is None:
         graph = device.type == "cuda" and generator is None
     loop = _DecodeLoop(model, cache, tok, pos, out, done, eos_token_id, sampling)
-    n = max_new_tokens - 1
-    if graph and n > 0:
-        loop.capture(warmup=min(2, n))
-    try:
-        for i in range(n):
-            if not graph:
-                cache.kv_len_max = max_len + i + 1  # known on the host: fewer idle workgroups
-            loop()
-            if eos_token_id is not None and (i + 1) % sync_every == 0 and bool(done.all()):
-                break
-    finally:
-        cache.kv_len_max = None  # the bound only held inside this call (a returned cache is reused later)
+    _run_decode(loop, max_new_tokens - 1, graph, max_len + 1, eos_token_id, sync_every)
     return (out, cache) if return_cache else out
 
 

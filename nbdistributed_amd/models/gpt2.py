@@ -117,6 +117,15 @@ class CausalSelfAttention(nn.Module):
         a = cache.attend(layer, qkv, pos)
         return ops.linear_small(a, self.c_proj.weight, self.c_proj.bias, residual=x)
 
+    def extend(self, h, cache, layer: int, start, nnew):
+        """A block of new tokens per sequence (continuing from a cache): ``c_proj(attn(h))`` with
+        ``cache.extend`` (append at ``start``, attend over the cache) in place of attention."""
+        from .. import ops
+
+        lin = ops.gemm_linear if self.hip_gemm else ops.linear
+        qkv = lin(h, self.c_attn.weight, self.c_attn.bias)
+        return lin(cache.extend(layer, qkv, start, nnew), self.c_proj.weight, self.c_proj.bias)
+
 
 class MLP(nn.Module):
     def __init__(self, c: GPT2Config):
@@ -394,6 +403,32 @@ class GPT2(nn.Module):
         # the first vocab_size rows of the (padded) table: a contiguous view, no copy
         w = self.lm_head.weight[:c.vocab_size]
         return ops.linear_small(x, w, norm=("ln", self.ln_f.weight, self.ln_f.bias, self.ln_f.eps))
+
+    @torch.no_grad()
+    def extend(self, idx: torch.Tensor, cache, start: torch.Tensor, nnew: torch.Tensor) -> torch.Tensor:
+        """Continue from ``cache``: ``idx`` [B, Tn] holds ``nnew[b]`` new tokens per sequence
+        (right-padded) at positions ``start[b] + i``; they are appended to ``cache`` and attend
+        over it.  Logits [B, V] at row ``nnew - 1``.  Device-side only.  The stack runs on the
+        forward's ops (add + LayerNorm, the GEMMs with their row padding); only attention differs."""
+        from .. import ops
+
+        c = self.config
+        B, Tn = idx.shape
+        pos = (start.view(B, 1) + self._positions(Tn, idx.device)[None, :]).clamp(0, c.n_positions - 1)
+        if self._fast_ok(idx):
+            x = ops.embedding_tok_pos(idx.reshape(1, -1), self.wte.weight, pos.reshape(-1), self.wpe.weight,
+                                      c.vocab_size).view(B, Tn, c.n_embd)
+        else:
+            x = self.wte(idx) + self.wpe(pos)
+        ln = self.h[0].ln_1
+        h = ops.layer_norm(x, ln.weight, ln.bias, ln.eps)
+        for i, blk in enumerate(self.h):
+            x, h = ops.add_layer_norm(x, blk.attn.extend(h, cache, i, start, nnew), blk.ln_2.weight, blk.ln_2.bias,
+                                      blk.ln_2.eps)
+            nxt = self.h[i + 1].ln_1 if i + 1 < c.n_layer else self.ln_f
+            x, h = ops.add_layer_norm(x, blk.mlp(h, fast=True), nxt.weight, nxt.bias, nxt.eps)
+        last = torch.gather(h, 1, (nnew - 1).clamp(0, Tn - 1).view(B, 1, 1).expand(B, 1, c.n_embd)).squeeze(1)
+        return self._logits(last)
 
     def generate(self, idx: torch.Tensor, max_new_tokens: int, **kw) -> torch.Tensor:
         """``generation.generate`` (KV cache, HIP decode attention, graph-captured decode loop)."""

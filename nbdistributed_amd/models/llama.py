@@ -243,6 +243,12 @@ class LlamaAttention(nn.Module):
         a = cache.attend(layer, qkv, pos, rope=rope)
         return ops.linear_small(a, self.o_proj.weight, self.o_proj.bias, residual=x)
 
+    def extend(self, h, cache, layer: int, start, nnew, rope):
+        """A block of new tokens per sequence (continuing from a cache): ``o_proj(attn(h))`` with
+        ``cache.extend`` (RoPE at ``start + i``, append, attend over the cache) in place of attention."""
+        qkv = ops.gemm_linear(h, self.qkv_proj.weight, self.qkv_proj.bias)
+        return ops.gemm_linear(cache.extend(layer, qkv, start, nnew, rope=rope), self.o_proj.weight, self.o_proj.bias)
+
 
 class LlamaMLP(nn.Module):
     def __init__(self, c: LlamaConfig):
@@ -761,6 +767,26 @@ class LlamaForCausalLM(_LlamaPreTrained):
             x = layer.self_attn.decode(x, layer.input_layernorm.weight, eps, cache, i, pos, rope)
             x = layer.mlp.decode(x, layer.post_attention_layernorm.weight, eps)
         return ops.linear_small(x, self.lm_head.weight, norm=("rms", m.norm.weight, eps))
+
+    @torch.no_grad()
+    def extend(self, input_ids, cache, start, nnew):
+        """Continue from ``cache``: ``input_ids`` [B, Tn] holds ``nnew[b]`` new tokens per sequence
+        (right-padded) at positions ``start[b] + i``; they are appended to ``cache`` and attend
+        over it.  Logits [B, V] at row ``nnew - 1``.  Device-side only.  The stack runs on the
+        forward's ops (add + RMSNorm, the GEMMs with their row padding); only attention differs."""
+        m, c = self.model, self.config
+        B, Tn = input_ids.shape
+        rope = m.rope(cache.t_max, input_ids.device)
+        eps = c.rms_norm_eps
+        ln0 = m.layers[0].input_layernorm
+        x, h = ops.embed_rms_norm(input_ids, m.embed_tokens.weight, ln0.weight, ln0.eps)
+        for i, layer in enumerate(m.layers):
+            nxt = m.layers[i + 1].input_layernorm if i + 1 < len(m.layers) else m.norm
+            a = layer.self_attn.extend(h, cache, i, start, nnew, rope)
+            x, h = ops.add_rms_norm(x, a, layer.post_attention_layernorm.weight, eps)
+            x, h = ops.add_rms_norm(x, layer.mlp(h), nxt.weight, eps)
+        last = torch.gather(h, 1, (nnew - 1).clamp(0, Tn - 1).view(B, 1, 1).expand(B, 1, h.shape[-1])).squeeze(1)
+        return self.lm_head(last)
 
     def generate(self, input_ids, max_new_tokens: int, **kw):
         """``generation.generate`` (KV cache, HIP decode attention, graph-captured decode loop)."""

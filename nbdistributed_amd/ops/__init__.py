@@ -32,6 +32,10 @@ linear_small (K14)     decode linear: LN/RMS prologue + x·Wᵀ (MFMA) +   small
 packed_bounds (K16)    position_ids of packed rows -> per-query start /  packed.hip (one wave per
                        per-key end of the document, for the document-    row); attn.hip SEG kernels
                        masked K7 kernels (attention_qkv(bounds=))
+append_attention (K17) a block of new tokens over a KV cache (multi-turn  append.hip (append_kv +
+                       continuation): RoPE + cache append at per-       fwd_kernel's body over the
+                       sequence offsets + causal attention over the      cache; attn_common.h)
+                       cache; device-side start / nnew
 =====================  ==============================================  =========================
 
 GPU tensors always go to the HIP kernels; if ``libnbd_ops.so`` cannot be loaded on a GPU box the
@@ -46,7 +50,8 @@ from .attention import PackedBounds, attention_qkv, flash_attention, flash_suppo
 from . import graddst
 from .bucket import (_ref_flatten, _ref_prereduce, _ref_unflatten, bucket_flatten, bucket_unflatten, local_prereduce,
                      plan_offsets, prereduce_into_bucket)
-from .decode import decode_attention, decode_attention_reference, linear_small, linear_small_reference
+from .decode import (append_attention, append_attention_reference, append_supported, decode_attention,
+                     decode_attention_reference, linear_small, linear_small_reference)
 from .embedding import embedding, embedding_tok_pos
 from .gemm import (block_graphs, block_graphs_memory, block_graphs_reset, block_graphs_stats, cast_buffers_memory,
                    gemm_linear, llama_block, mlp_gelu, mlp_swiglu)
@@ -66,7 +71,7 @@ def __getattr__(name):
 
 
 __all__ = ["linear_tiny", "bucket_flatten", "bucket_unflatten", "local_prereduce", "prereduce_into_bucket", "graddst", "adamw_flat", "cross_entropy", "linear_cross_entropy",
-           "flash_attention", "attention_qkv", "decode_attention", "decode_attention_reference", "linear_small", "linear_small_reference", "flash_supported", "layer_norm", "add_layer_norm", "linear",
+           "flash_attention", "attention_qkv", "decode_attention", "decode_attention_reference", "append_attention", "append_attention_reference", "append_supported", "linear_small", "linear_small_reference", "flash_supported", "layer_norm", "add_layer_norm", "linear",
            "colsum", "embedding", "embedding_tok_pos", "gemm_linear", "llama_block", "block_graphs", "block_graphs_memory", "block_graphs_reset", "block_graphs_stats", "cast_buffers_memory", "mlp_gelu", "mlp_swiglu", "rms_norm", "add_rms_norm", "embed_rms_norm", "tokpos_layer_norm", "rope_", "rope_tables", "swiglu", "tensor_summary",
            "tensor_summary_text", "tensor_summary_raw", "plan_offsets", "native_available", "load_library",
            "SUMMARY_FIELDS", "seqcls_prep", "packed_bounds", "PackedBounds"]

@@ -2,6 +2,8 @@
 
 ``csrc/kernels/decode.hip`` on GPU (bf16, head dim 64, up to 8 query heads per key/value head);
 the same math in PyTorch otherwise (CPU, fp32) — also the numerics reference of the GPU tests.
+Block append (K17, ``csrc/kernels/append.hip``): several new tokens per sequence at per-sequence
+offsets — what continuing from a returned cache runs instead of a second prefill.
 """
 from __future__ import annotations
 
@@ -86,6 +88,93 @@ def decode_attention(qkv, k_cache, v_cache, pos, n_head: int, scale: Optional[fl
         return torch.ops.nbd.decode_attn(qkv, k_cache, v_cache, pos, int(n_head), sc, int(kv_len_max or Tmax),
                                          cos, sin, workspace)
     return decode_attention_reference(qkv, k_cache, v_cache, pos, n_head, sc, rope)
+
+
+# ------------------------------------------------------------------ block append (K17)
+def append_supported(qkv, k_cache, n_head: int) -> bool:
+    import torch
+
+    Hkv = k_cache.shape[1]
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16
+            and k_cache.shape[-1] == 64 and n_head % Hkv == 0)
+
+
+def _append_span(start, nnew, Tn: int, limit: int):
+    """``start`` / ``nnew`` clamped as the kernel clamps them before addressing: 0 ≤ start ≤ limit-1,
+    0 ≤ nnew ≤ min(Tn, limit - start)."""
+    import torch
+
+    start = start.long().clamp(0, limit - 1)
+    return start, torch.minimum(nnew.long().clamp(0, Tn), limit - start)
+
+
+def append_attention_reference(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Optional[float] = None,
+                               rope=None, kv_len_max: Optional[int] = None):
+    """PyTorch version of :func:`append_attention` (fp32 math, writes the caches the same way)."""
+    import torch
+
+    B, Tn, W = qkv.shape
+    Hkv, Tmax, D = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
+    H, G = n_head, n_head // Hkv
+    dev = qkv.device
+    sc = float(scale) if scale is not None else D ** -0.5
+    start, nnew = _append_span(start, nnew, Tn, min(Tmax, int(kv_len_max or Tmax)))
+    i = torch.arange(Tn, device=dev)
+    valid = i[None, :] < nnew[:, None]  # [B, Tn]
+    pos = (start[:, None] + i[None, :]).clamp(max=Tmax - 1)  # (clamped only on padding rows)
+    q = qkv[..., : H * D].reshape(B, Tn, H, D).float()
+    k = qkv[..., H * D:(H + Hkv) * D].reshape(B, Tn, Hkv, D).float()
+    v = qkv[..., (H + Hkv) * D:].reshape(B, Tn, Hkv, D)
+    if rope is not None:
+        half = D // 2
+        c, s = rope[0][pos][:, :, None, :].float(), rope[1][pos][:, :, None, :].float()
+
+        def rot(x):
+            a, b = x[..., :half], x[..., half:]
+            return torch.cat([a * c - b * s, b * c + a * s], -1)
+
+        q, k = rot(q), rot(k)
+    bi, ti = valid.nonzero(as_tuple=True)
+    k_cache[bi, :, pos[bi, ti]] = k[bi, ti].to(k_cache.dtype)
+    v_cache[bi, :, pos[bi, ti]] = v[bi, ti].to(v_cache.dtype)
+    # rows >= start + nnew hold nothing of this sequence (possibly NaN): zeros, and masked below
+    t = torch.arange(Tmax, device=dev)
+    held = (t[None, :] < (start + nnew)[:, None])[:, None, :, None]  # [B, 1, Tmax, 1]
+    kc = torch.where(held, k_cache.float(), torch.zeros((), device=dev))
+    vc = torch.where(held, v_cache.float(), torch.zeros((), device=dev))
+    s = torch.einsum("btkgd,bksd->bkgts", q.reshape(B, Tn, Hkv, G, D), kc) * sc  # [B, Hkv, G, Tn, Tmax]
+    mask = t[None, None, :] > pos[:, :, None]  # [B, Tn, Tmax]
+    p = torch.softmax(s.masked_fill(mask[:, None, None], float("-inf")), -1)
+    o = torch.einsum("bkgts,bksd->btkgd", p, vc).reshape(B, Tn, H * D)
+    return o.masked_fill(~valid[:, :, None], 0.0).to(qkv.dtype)
+
+
+def append_attention(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Optional[float] = None, rope=None,
+                     kv_len_max: Optional[int] = None):
+    """Attention of a block of new tokens per sequence over its KV cache (multi-turn append).
+
+    ``qkv`` [B, Tn, (H + 2·Hkv)·D] is the new tokens' packed projection (any ``Tn`` ≥ 1: the kernel
+    wants no padding of it), ``k_cache``/``v_cache`` [B, Hkv, Tmax, D] the caches, ``start`` int64
+    [B] (on the device) the rows already valid in each, ``nnew`` int64 [B] the real rows of ``qkv``
+    (1 ≤ nnew[b] ≤ Tn; rows past it are padding).  For i < nnew[b] the new k (rotated at position
+    start[b] + i when ``rope`` = (cos, sin) tables) and v are written to cache row start[b] + i and
+    query i attends rows 0..start[b] + i; no later row influences it, whatever it holds, and rows
+    ≥ start[b] + nnew[b] are not written.  ``kv_len_max`` is a host bound on max(start + nnew)
+    (default Tmax).  Returns [B, Tn, H·D] with exact zeros on the padding rows.  GPU bf16, head dim
+    64 → ``csrc/kernels/append.hip``; elsewhere the same math in PyTorch."""
+    import torch
+
+    D = k_cache.shape[-1]
+    sc = float(scale) if scale is not None else D ** -0.5
+    if append_supported(qkv, k_cache, n_head):
+        _require()
+        Tmax = k_cache.shape[2]
+        cos, sin = rope if rope is not None else (None, None)
+        if qkv.stride(-1) != 1 or qkv.stride(0) % 8 or qkv.stride(1) % 8 or qkv.data_ptr() % 16:
+            qkv = qkv.contiguous()
+        return torch.ops.nbd.append_attn(qkv, k_cache, v_cache, start, nnew, int(n_head), sc,
+                                         int(kv_len_max or Tmax), cos, sin)
+    return append_attention_reference(qkv, k_cache, v_cache, start, nnew, n_head, sc, rope, kv_len_max)
 
 
 # ------------------------------------------------------------------ small-M fused linear (K14)

@@ -353,6 +353,10 @@ class CPCausalSelfAttention(torch.nn.Module):
         y = ring_attention(q, k, v, causal=True, group=self.group, layout=self.layout)
         return lin(y.transpose(1, 2).reshape(B, T, C), self.c_proj.weight, self.c_proj.bias)
 
+    def extend(self, *args, **kwargs):
+        raise NotImplementedError("continuing generation from a KV cache (generate(..., cache=)) is not implemented "
+                                  "under context parallelism")
+
 
 def parallelize_gpt2_context(model, group=None, layout: str = "contiguous"):
     """Context parallelism for a (replicated) ``models.GPT2`` in place: every rank feeds its
@@ -400,6 +404,10 @@ class CPLlamaAttention(torch.nn.Module):
         v = qkv[:, :, (H + Hkv) * D:].view(B, T, Hkv, D).transpose(1, 2)
         y = ring_attention(q, k, v, causal=True, group=self.group, layout=self.layout)
         return ops.gemm_linear(y.transpose(1, 2).reshape(B, T, H * D), self.o_proj.weight)
+
+    def extend(self, *args, **kwargs):
+        raise NotImplementedError("continuing generation from a KV cache (generate(..., cache=)) is not implemented "
+                                  "under context parallelism")
 
 
 def parallelize_llama_context(model, group=None, layout: str = "contiguous"):

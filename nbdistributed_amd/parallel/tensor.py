@@ -237,6 +237,10 @@ class TPCausalSelfAttention(nn.Module):
             dist.all_reduce(y, group=self.group)
         return y
 
+    def extend(self, *args, **kwargs):
+        raise NotImplementedError("continuing generation from a KV cache (generate(..., cache=)) is not implemented "
+                                  "under tensor parallelism")
+
 
 class TPMLP(nn.Module):
     """GPT-2 MLP with this rank's hidden features: ``c_fc`` column-parallel, GELU on the shard,
@@ -314,6 +318,10 @@ class TPLlamaAttention(nn.Module):
         if _size(self.group) > 1:
             dist.all_reduce(y, group=self.group)
         return y
+
+    def extend(self, *args, **kwargs):
+        raise NotImplementedError("continuing generation from a KV cache (generate(..., cache=)) is not implemented "
+                                  "under tensor parallelism")
 
 
 class TPLlamaMLP(nn.Module):
