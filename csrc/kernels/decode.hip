@@ -166,7 +166,10 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
     auto compute = [&](const int (&j)[U], u32x4 (&kr)[U], u32x4 (&vr)[U]) {
 #pragma unroll
       for (int u = 0; u < U; ++u)
-        if (j[u] == pos) {  // the new token: its row in memory may predate this launch's write
+        // the new token: its row in memory may predate this launch's write.  A masked key
+        // (j > pos) takes the register copy too: with c0 == pos its load above fetched that same
+        // stale row, and 0 · v is NaN when the free row holds NaN or ±inf
+        if (j[u] >= pos) {
           kr[u] = knew;
           vr[u] = vnew;
         }

@@ -298,6 +298,8 @@ at::Tensor linear_small_hip(const at::Tensor& x, const at::Tensor& w, const c10:
   TORCH_CHECK(norm >= 0 && norm <= 2 && act >= 0 && act <= 2, "linear_small: bad norm / act");
   const bool swiglu = act == ACT_SWIGLU;
   TORCH_CHECK(!swiglu || w.size(0) % 2 == 0, "linear_small: SwiGLU needs w = [gate; up]");
+  // the epilogue adds the bias to the gate before silu; nothing defines that, so it is refused
+  TORCH_CHECK(!swiglu || !(bias.has_value() && bias->defined()), "linear_small: no bias with SwiGLU");
   const int64_t N = swiglu ? w.size(0) / 2 : w.size(0);
   TORCH_CHECK(N >= 1 && N < (1LL << 31) / 16, "linear_small: bad N");
   auto opt_bf16 = [&](const c10::optional<at::Tensor>& t, int64_t n, const char* name) -> const uint16_t* {

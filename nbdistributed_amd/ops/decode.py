@@ -54,11 +54,15 @@ def decode_attention_reference(qkv, k_cache, v_cache, pos, n_head: int, scale: O
     bi = torch.arange(B, device=qkv.device)
     k_cache[bi, :, pos] = k.to(k_cache.dtype)
     v_cache[bi, :, pos] = v.to(v_cache.dtype)
-    s = torch.einsum("bkgd,bktd->bkgt", q.float().view(B, Hkv, G, D), k_cache.float()) * sc
     mask = torch.arange(Tmax, device=qkv.device)[None, :] > pos[:, None]  # [B, Tmax]
+    # rows > pos hold nothing of this sequence (possibly NaN): zeros, and masked below
+    held = ~mask[:, None, :, None]
+    kc = torch.where(held, k_cache.float(), torch.zeros((), device=qkv.device))
+    vc = torch.where(held, v_cache.float(), torch.zeros((), device=qkv.device))
+    s = torch.einsum("bkgd,bktd->bkgt", q.float().view(B, Hkv, G, D), kc) * sc
     s = s.masked_fill(mask[:, None, None, :], float("-inf"))
     p = torch.softmax(s, -1)
-    o = torch.einsum("bkgt,bktd->bkgd", p, v_cache.float())
+    o = torch.einsum("bkgt,bktd->bkgd", p, vc)
     return o.reshape(B, H * D).to(qkv.dtype)
 
 

@@ -156,11 +156,15 @@ def test_linear_small_matches_reference(M, norm, act, bias, res):
 
 
 def test_linear_small_ragged_vocab_head():
-    # LM-head shape: odd N (ragged last column tile), LayerNorm prologue, grid capped at 512 tiles
-    x, w, _, nrm, _ = _lin_case(8, 768, 50257, "ln", "none", False, False, seed=3)
-    y = ops.linear_small(x, w, norm=nrm)
-    ref = ops.linear_small_reference(x, w, norm=nrm).float()
-    assert ((y.float() - ref).abs().max() / ref.abs().max()).item() < 2e-2
+    # LM-head shape: odd N (ragged last column tile), LayerNorm.  At M = 8 (>= LIBRARY_MIN_ROWS, N >=
+    # LIBRARY_MIN_N) ``ops.linear_small`` runs the stand-alone norm kernel and the library GEMM, not
+    # smallm.hip; at M = 3 it reaches the kernel: fused LayerNorm prologue, grid capped at 512
+    # workgroups looping over 3142 tiles (tests/test_gpu_decode_paths.py checks that loop per tile)
+    for M in (8, 3):
+        x, w, _, nrm, _ = _lin_case(M, 768, 50257, "ln", "none", False, False, seed=3)
+        y = ops.linear_small(x, w, norm=nrm)
+        ref = ops.linear_small_reference(x, w, norm=nrm).float()
+        assert ((y.float() - ref).abs().max() / ref.abs().max()).item() < 2e-2, M
 
 
 @pytest.mark.parametrize("V,offset", [(50257, 0), (512, 0), (1001, 3)])
