@@ -12,6 +12,14 @@ and GPT-2-small shapes, rounds of the two interleaved.
 
     python benchmarks/generate_bench.py --continue [--models smollm2,gpt2] [--batches 1,8]
         [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
+
+``--kv-dtype fp8``: an fp8 (e4m3fn, no scales) KV-cache arm beside the bf16 arm, same process, same
+weights, rounds interleaved: marginal ms per token at ``--prompt`` and at the longest history each
+model allows, the decode kernel alone for both caches, and the fp8 cache's logits and greedy
+tokens against the bf16 cache's.
+
+    python benchmarks/generate_bench.py --kv-dtype fp8 [--models smollm2,gpt2] [--batches 1,8,32]
+        [--prompt 128] [--new 256] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -38,14 +46,14 @@ def timed(fn, reps=2):
     return best
 
 
-def kernel_bench(rows):
+def kernel_bench(rows, kv_dtype=torch.bfloat16):
     from nbdistributed_amd import ops
     from nbdistributed_amd.ops.decode import partials_numel
 
     out = []
     for B, H, Hkv, T in rows:
-        kc = torch.randn(B, Hkv, T, 64, device="cuda").to(torch.bfloat16)
-        vc = torch.randn_like(kc)
+        kc = torch.randn(B, Hkv, T, 64, device="cuda").to(torch.bfloat16).to(kv_dtype)
+        vc = torch.randn(B, Hkv, T, 64, device="cuda").to(torch.bfloat16).to(kv_dtype)
         qkv = torch.randn(B, (H + 2 * Hkv) * 64, device="cuda").to(torch.bfloat16)
         pos = torch.full((B,), T - 1, device="cuda", dtype=torch.int64)
         ws = torch.empty(partials_numel(B, H, T), dtype=torch.float32, device="cuda")
@@ -61,8 +69,10 @@ def kernel_bench(rows):
         e.record()
         e.synchronize()
         us = s.elapsed_time(e) / n * 1e3
-        gbs = 2 * kc.numel() * 2 / us / 1e3
+        gbs = 2 * kc.numel() * kc.element_size() / us / 1e3
         r = dict(B=B, H=H, Hkv=Hkv, T=T, us=round(us, 2), cache_GBps=round(gbs, 1))
+        if kv_dtype != torch.bfloat16:
+            r["kv_dtype"] = str(kv_dtype).replace("torch.", "")
         print(json.dumps(r), flush=True)
         out.append(r)
     return out
@@ -128,8 +138,103 @@ def continue_bench(a):
             json.dump(res, f, indent=1)
 
 
+def _bench_model(name, room):
+    """(model, vocab, position limit, (H, Hkv)): random-init bf16, GPT-2 small or SmolLM2-135M shapes."""
+    from nbdistributed_amd.models import GPT2, GPT2Config, SMOLLM2_135M
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+
+    torch.manual_seed(0)
+    if name == "smollm2":
+        cfg = {k: v for k, v in SMOLLM2_135M.items() if k != "hidden_act"}
+        m, vocab, limit, heads = LlamaForCausalLM(LlamaConfig(**cfg)), cfg["vocab_size"], min(
+            room, cfg["max_position_embeddings"]), (cfg["num_attention_heads"], cfg["num_key_value_heads"])
+    else:
+        m, vocab, limit, heads = GPT2(GPT2Config.small()), 50257, 1024, (12, 12)
+    return m.to("cuda", torch.bfloat16).eval(), vocab, limit, heads
+
+
+def kv_dtype_bench(a):
+    """An fp8 KV-cache arm beside the bf16 arm: same process, same weights, rounds interleaved.
+    Per (model, batch, prompt): the marginal ms per token of graphed decoding (two lengths, prefill
+    and capture cancel) for both caches; per model: the decode kernel alone at the longest history;
+    and the quality of the fp8 cache against the bf16 one over ``--new`` teacher-forced decode steps
+    (max |Δlogit|, arg-max agreement) and the free-running greedy tokens."""
+    import statistics
+
+    from nbdistributed_amd.generation import KVCache, generate
+
+    arms = (("bf16", None), ("fp8", torch.float8_e4m3fn))
+    res = {"what": "decode with an fp8 (e4m3fn, no scales) KV cache vs the bf16 cache: marginal ms per token of "
+                   "graphed generate, rounds interleaved", "new_tokens": a.new, "rounds": a.rounds, "points": [],
+           "decode_kernel": [], "quality": []}
+    for name in a.models.split(","):
+        m, vocab, limit, (H, Hkv) = _bench_model(name, a.max_positions)
+        longest = limit - (32 + a.new)
+        for B in [int(x) for x in a.batches.split(",")]:
+            for prompt in sorted({min(a.prompt, longest), longest}):
+                ids = torch.randint(1, vocab, (B, prompt), device="cuda")
+                outs, ts = {}, {arm: ([], []) for arm, _ in arms}
+                for arm, kd in arms:  # warm-up of both lengths; the long run's tokens for the agreement
+                    generate(m, ids, 32, graph=True, kv_dtype=kd)
+                    outs[arm] = generate(m, ids, 32 + a.new, graph=True, kv_dtype=kd)
+                for _ in range(a.rounds):
+                    for arm, kd in arms:
+                        for n, sink in ((32, ts[arm][0]), (32 + a.new, ts[arm][1])):
+                            torch.cuda.synchronize()
+                            t = time.perf_counter()
+                            generate(m, ids, n, graph=True, kv_dtype=kd)
+                            torch.cuda.synchronize()
+                            sink.append((time.perf_counter() - t) * 1e3)
+                row = dict(model=name, batch=B, prompt=prompt, history_end=prompt + 32 + a.new)
+                for arm, _ in arms:
+                    per = [(lo - sh) / a.new for sh, lo in zip(*ts[arm])]
+                    row[arm + "_ms_per_token"] = round(statistics.median(per), 4)
+                    row[arm + "_ms_per_token_min_max"] = [round(min(per), 4), round(max(per), 4)]
+                row["fp8_over_bf16"] = round(row["fp8_ms_per_token"] / row["bf16_ms_per_token"], 3)
+                same = (outs["bf16"][:, prompt:] == outs["fp8"][:, prompt:]).float()
+                row["greedy_tokens_equal_frac"] = round(float(same.mean()), 3)
+                row["greedy_tokens_agreeing_prefix_mean"] = round(float(same.cumprod(-1).sum(-1).mean()), 1)
+                print(json.dumps(row), flush=True)
+                res["points"].append(row)
+        # the decode kernel alone, one layer's cache at the longest history
+        for B in [int(x) for x in a.batches.split(",")]:
+            for dt in (torch.bfloat16, torch.float8_e4m3fn):
+                r = kernel_bench([(B, H, Hkv, limit)], dt)[0]
+                r["model"] = name
+                res["decode_kernel"].append(r)
+        # quality, teacher-forced on the bf16 arm's own greedy tokens: both caches see the same inputs
+        B, prompt = 8, min(a.prompt, longest)
+        ids = torch.randint(1, vocab, (B, prompt), device="cuda")
+        seq = generate(m, ids, a.new + 1, graph=True)
+        t_pad = m.prefill_length(prompt)
+        caches = [KVCache.for_model(m, B, max(t_pad, prompt + a.new + 1), dtype=dt) for dt in (None, torch.float8_e4m3fn)]
+        lens = torch.full((B,), prompt, dtype=torch.int64, device="cuda")
+        padded = torch.nn.functional.pad(ids, (0, t_pad - prompt))
+        for c in caches:
+            m.prefill(padded, c, lens)
+        dmax, lmax, agree = 0.0, 0.0, 0
+        for t in range(prompt, prompt + a.new):
+            pos = torch.full((B,), t, dtype=torch.int64, device="cuda")
+            l16, l8 = (m.decode_step(seq[:, t], pos, c).float() for c in caches)
+            dmax, lmax = max(dmax, float((l16 - l8).abs().max())), max(lmax, float(l16.abs().max()))
+            agree += int((l16.argmax(-1) == l8.argmax(-1)).sum())
+        q = dict(model=name, batch=B, prompt=prompt, steps=a.new, max_abs_logit_diff=round(dmax, 4),
+                 max_abs_logit=round(lmax, 3), argmax_agreement=round(agree / (B * a.new), 4))
+        print(json.dumps(q), flush=True)
+        res["quality"].append(q)
+        del m, caches
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--kv-dtype", dest="kv_dtype", default=None, choices=["fp8"],
+                    help="add an fp8 KV-cache arm beside the bf16 arm (same process, same weights): --models, "
+                         "--batches, --prompt and the longest history each model allows, --new, --rounds")
+    ap.add_argument("--max-positions", type=int, default=8192, help="--kv-dtype: cap on the longest history")
     ap.add_argument("--continue", dest="cont", action="store_true", help="the multi-turn arm (see the module docstring)")
     ap.add_argument("--models", default="smollm2,gpt2")
     ap.add_argument("--hist", default="512,2048,4096")
@@ -146,6 +251,8 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.kv_dtype:
+        return kv_dtype_bench(a)
     if a.cont:
         if a.batches == "1,8,32":
             a.batches = "1,8"

@@ -22,6 +22,14 @@
 //     L2s are not coherent with each other — and measured 3-10x slower than the extra launch.)
 //     The grid shapes depend only on the host's key bound, so a decode step captures into a HIP
 //     graph with the positions living on the device.
+//
+// fp8 caches (`decode_kernel<G, true>`): a cache row is 64 B of OCP e4m3fn, no scales; it holds
+// q8(r) = round-to-nearest-even(clamp(r, ±448)) of the bf16 row r a bf16 cache would hold (NaN
+// stays NaN), so the rotated k is rounded twice, fp32 -> bf16 -> e4m3, like a prefilled row.  Only
+// the loads and the one store differ: a lane holds its 8 dims as 8 B, a lane group covers one 64-B
+// row, one wave instruction reads 512 contiguous bytes; v_cvt_pk_f32_fp8 unpacks into the same fp32
+// lanes.  The new token's register copy is the stored bytes, so it attends to its own key and
+// value as every later step will read them.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -44,8 +52,8 @@ constexpr float kLog2e = 1.4426950408889634f;
 struct Params {
   const uint16_t* qkv;  // [B, W] bf16 rows (row stride qkv_ld elements)
   int64_t qkv_ld;
-  uint16_t* kc;  // [B, Hkv, Tmax, 64] bf16
-  uint16_t* vc;
+  void* kc;  // [B, Hkv, Tmax, 64] bf16, or e4m3fn (decode_kernel<G, true>)
+  void* vc;
   const int64_t* pos;  // [B]
   const float* cos;    // [>= Tmax, 32] or nullptr
   const float* sin;
@@ -84,6 +92,52 @@ __device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
   return w;
 }
 
+// a lane's 8 dims of a cache row: 16 B of bf16 or 8 B of e4m3fn; either way a row is 8 of them
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+template <bool F8>
+struct Row {
+  using type = u32x4;
+};
+template <>
+struct Row<true> {
+  using type = u32x2;
+};
+
+__device__ __forceinline__ void unpack8(const u32x2& w, float (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false);  // bytes 0, 1
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);   // bytes 2, 3
+    v[4 * j] = lo[0];
+    v[4 * j + 1] = lo[1];
+    v[4 * j + 2] = hi[0];
+    v[4 * j + 3] = hi[1];
+  }
+}
+
+// q8 of 8 bf16 values: clamp to ±448 (±inf saturates; e4m3fn has no inf), round to nearest even.
+// NaN is kept out of the clamp (fminf / fmaxf — v_min / v_max / v_med3 — return the other operand)
+// and its byte is written here, 0x7f with the sign: what a cast makes of NaN is then no question.
+__device__ __forceinline__ u32x2 quant8(const u32x4& w) {
+  float f[8];
+  unpack8(w, f);
+  float c[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) c[e] = f[e] != f[e] ? 0.f : fminf(fmaxf(f[e], -448.f), 448.f);
+  u32x2 r;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    int x = 0;
+    x = __builtin_amdgcn_cvt_pk_fp8_f32(c[4 * j], c[4 * j + 1], x, false);
+    x = __builtin_amdgcn_cvt_pk_fp8_f32(c[4 * j + 2], c[4 * j + 3], x, true);
+    r[j] = (uint32_t)x;
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e)
+    if (f[e] != f[e]) r[e >> 2] |= (0x7fu | (__float_as_uint(f[e]) >> 31 << 7)) << (8 * (e & 3));
+  return r;
+}
+
 // HF rotate_half RoPE on this lane's 8 dims [8·d8, 8·d8+8); the partner dims (±32) sit in lane d8^4
 __device__ __forceinline__ void rope_lane(float (&x)[8], const float* cos, const float* sin, int64_t t, int d8) {
   const float4* c4 = reinterpret_cast<const float4*>(cos + t * 32 + (d8 & 3) * 8);
@@ -99,9 +153,13 @@ __device__ __forceinline__ void rope_lane(float (&x)[8], const float* cos, const
   }
 }
 
-template <int G>
+template <int G, bool F8>
 __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
-  constexpr int U = G <= 4 ? 4 : 2;  // keys in flight per group
+  // keys in flight per group.  The same on an fp8 cache, though a load is half the bytes: twice
+  // the keys measured equal at G = 1, 4-30 % slower at G = 3, 4 and 8 (G = 4, 8: over 256 VGPRs)
+  // and 3 % faster in the one G = 6 shape tried (docs/FINDINGS.md)
+  constexpr int U = G <= 4 ? 4 : 2;
+  using row_t = typename Row<F8>::type;
   __shared__ float sm_m[NW][G], sm_l[NW][G];
   __shared__ float sm_o[NW][G][D];
 
@@ -126,17 +184,29 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
     for (int e = 0; e < 8; ++e) q[g][e] *= p.scale2;
   }
   const int64_t head_base = ((int64_t)b * p.Hkv + kvh) * p.Tmax * D;
-  u32x4 knew, vnew;
+  // the new row as stored: on an fp8 cache the bf16 row is quantised here and the register copy
+  // is those bytes, so the token attends to its own key and value as later steps will read them
+  row_t knew, vnew;
   {
     float kf[8];
     load8<bf16_t>(reinterpret_cast<const bf16_t*>(row + (p.H + kvh) * D + d8 * 8), kf);
     if (p.cos != nullptr) rope_lane(kf, p.cos, p.sin, pos, d8);
-    knew = pack8(kf);
-    vnew = *reinterpret_cast<const u32x4*>(row + (p.H + p.Hkv + kvh) * D + d8 * 8);
+    const u32x4 kw = pack8(kf);
+    const u32x4 vw = *reinterpret_cast<const u32x4*>(row + (p.H + p.Hkv + kvh) * D + d8 * 8);
+    if constexpr (F8) {
+      knew = quant8(kw);
+      vnew = quant8(vw);
+    } else {
+      knew = kw;
+      vnew = vw;
+    }
   }
+  // a row is 8 row_t (one per lane of a group) in either format
+  row_t* const kbase = static_cast<row_t*>(p.kc) + head_base / 8 + d8;
+  row_t* const vbase = static_cast<row_t*>(p.vc) + head_base / 8 + d8;
   if (c0 <= pos && pos < c0 + p.chunk && grp == 0) {  // this chunk owns the new row
-    *reinterpret_cast<u32x4*>(p.kc + head_base + (int64_t)pos * D + d8 * 8) = knew;
-    *reinterpret_cast<u32x4*>(p.vc + head_base + (int64_t)pos * D + d8 * 8) = vnew;
+    kbase[(int64_t)pos * 8] = knew;
+    vbase[(int64_t)pos * 8] = vnew;
   }
 
   float m[G], l[G], o[G][8];
@@ -149,21 +219,21 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   }
 
   if (c0 < c1) {
-    const uint16_t* kb = p.kc + head_base + d8 * 8;
-    const uint16_t* vb = p.vc + head_base + d8 * 8;
+    const row_t* kb = kbase;
+    const row_t* vb = vbase;
     const int iters = (c1 - c0 + NG * U - 1) / (NG * U);
     // two register buffers: the keys / values of iteration it+1 are in flight while iteration it
     // is computed (a chunk is only a few iterations long, so each exposed round trip shows)
-    auto load = [&](int it, int (&j)[U], u32x4 (&kr)[U], u32x4 (&vr)[U]) {
+    auto load = [&](int it, int (&j)[U], row_t (&kr)[U], row_t (&vr)[U]) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         j[u] = c0 + grp + NG * (it * U + u);
         const int jj = j[u] < c1 ? j[u] : c0;  // in-bounds address for a masked key
-        kr[u] = *reinterpret_cast<const u32x4*>(kb + (int64_t)jj * D);
-        vr[u] = *reinterpret_cast<const u32x4*>(vb + (int64_t)jj * D);
+        kr[u] = kb[(int64_t)jj * 8];
+        vr[u] = vb[(int64_t)jj * 8];
       }
     };
-    auto compute = [&](const int (&j)[U], u32x4 (&kr)[U], u32x4 (&vr)[U]) {
+    auto compute = [&](const int (&j)[U], row_t (&kr)[U], row_t (&vr)[U]) {
 #pragma unroll
       for (int u = 0; u < U; ++u)
         // the new token: its row in memory may predate this launch's write.  A masked key
@@ -210,7 +280,7 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
       }
     };
     int ja[U], jb[U];
-    u32x4 ka[U], va[U], kbuf[U], vbuf[U];
+    row_t ka[U], va[U], kbuf[U], vbuf[U];
     load(0, ja, ka, va);
     for (int it = 0; it < iters; it += 2) {
       if (it + 1 < iters) load(it + 1, jb, kbuf, vbuf);
@@ -321,11 +391,20 @@ at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1 &&
                   qkv.stride(0) % 8 == 0 && ((uintptr_t)qkv.data_ptr() & 15) == 0,
               "decode_attn: qkv must be a bf16 [B, (H + 2·Hkv)·64] GPU view, unit last stride, 16-B aligned rows");
-  TORCH_CHECK(k_cache.is_cuda() && k_cache.scalar_type() == at::kBFloat16 && k_cache.is_contiguous() &&
-                  k_cache.dim() == 4 && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes() &&
-                  v_cache.scalar_type() == at::kBFloat16 && v_cache.is_contiguous() &&
-                  ((uintptr_t)k_cache.data_ptr() & 15) == 0 && ((uintptr_t)v_cache.data_ptr() & 15) == 0,
-              "decode_attn: caches must be contiguous bf16 [B, Hkv, Tmax, 64]");
+  const bool f8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  if (f8) {
+    TORCH_CHECK(k_cache.is_cuda() && k_cache.is_contiguous() && k_cache.dim() == 4 && k_cache.size(3) == D &&
+                    v_cache.sizes() == k_cache.sizes() && v_cache.scalar_type() == at::kFloat8_e4m3fn &&
+                    v_cache.is_contiguous() && ((uintptr_t)k_cache.data_ptr() & 7) == 0 &&
+                    ((uintptr_t)v_cache.data_ptr() & 7) == 0,
+                "decode_attn: fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, 64], 8-B aligned rows");
+  } else {
+    TORCH_CHECK(k_cache.is_cuda() && k_cache.scalar_type() == at::kBFloat16 && k_cache.is_contiguous() &&
+                    k_cache.dim() == 4 && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes() &&
+                    v_cache.scalar_type() == at::kBFloat16 && v_cache.is_contiguous() &&
+                    ((uintptr_t)k_cache.data_ptr() & 15) == 0 && ((uintptr_t)v_cache.data_ptr() & 15) == 0,
+                "decode_attn: caches must be contiguous bf16 [B, Hkv, Tmax, 64]");
+  }
   const int64_t B = qkv.size(0), Hkv = k_cache.size(1), Tmax = k_cache.size(2), H = n_head;
   TORCH_CHECK(k_cache.size(0) == B, "decode_attn: cache batch ", k_cache.size(0), " != ", B);
   TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && H / Hkv <= 8, "decode_attn: need H % Hkv == 0 and H / Hkv <= 8");
@@ -351,8 +430,8 @@ at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
   Params p;
   p.qkv = static_cast<const uint16_t*>(qkv.data_ptr());
   p.qkv_ld = qkv.stride(0);
-  p.kc = static_cast<uint16_t*>(k_cache.data_ptr());
-  p.vc = static_cast<uint16_t*>(v_cache.data_ptr());
+  p.kc = k_cache.data_ptr();
+  p.vc = v_cache.data_ptr();
   p.pos = pos.data_ptr<int64_t>();
   p.cos = hc ? rope_cos->data_ptr<float>() : nullptr;
   p.sin = hc ? rope_sin->data_ptr<float>() : nullptr;
@@ -369,9 +448,12 @@ at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
   hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   const dim3 grid((unsigned)(B * Hkv * nchunks));
   switch (H / Hkv) {
-#define NBD_DECODE_G(g) \
-  case g:               \
-    hipLaunchKernelGGL((decode_kernel<g>), grid, dim3(NT), 0, st, p); \
+#define NBD_DECODE_G(g)                                                        \
+  case g:                                                                      \
+    if (f8)                                                                    \
+      hipLaunchKernelGGL((decode_kernel<g, true>), grid, dim3(NT), 0, st, p);  \
+    else                                                                       \
+      hipLaunchKernelGGL((decode_kernel<g, false>), grid, dim3(NT), 0, st, p); \
     break;
     NBD_DECODE_G(1)
     NBD_DECODE_G(2)

@@ -33,8 +33,21 @@ from typing import Optional
 import torch
 
 
+def _kv_dtype(kv_dtype):
+    """``generate``'s ``kv_dtype``: None (the model's dtype), "fp8" or ``torch.float8_e4m3fn``."""
+    if kv_dtype is None or kv_dtype == torch.float8_e4m3fn:
+        return kv_dtype
+    if isinstance(kv_dtype, str) and kv_dtype.lower() == "fp8":
+        return torch.float8_e4m3fn
+    raise ValueError(f"generate: kv_dtype must be None, 'fp8' or torch.float8_e4m3fn, got {kv_dtype!r}")
+
+
 class KVCache:
-    """k / v caches [n_layer, B, Hkv, t_max, D] plus the decode kernel's workspace."""
+    """k / v caches [n_layer, B, Hkv, t_max, D] plus the decode kernel's workspace.
+
+    ``dtype=torch.float8_e4m3fn``: rows are stored as ``ops.decode.q8`` makes them (clamped to
+    ±448, round to nearest even, no scales) by ``store`` and by ``attend`` alike: half the bytes
+    held and half the bytes a decode step streams.  ``extend`` (continue) takes no fp8 cache."""
 
     def __init__(self, n_layer: int, batch: int, n_head: int, n_kv: int, t_max: int, head_dim: int,
                  dtype=torch.bfloat16, device="cuda"):
@@ -61,6 +74,10 @@ class KVCache:
     def nbytes(self) -> int:
         return 2 * self.k.numel() * self.k.element_size()
 
+    @property
+    def is_fp8(self) -> bool:
+        return self.k.dtype == torch.float8_e4m3fn
+
     def store(self, layer: int, qkv: torch.Tensor, rope=None) -> None:
         """Prefill: copy k (rotated by ``rope`` = (cos, sin)) and v of a packed [B, T, W]
         projection into positions [0, T) of ``layer``."""
@@ -73,8 +90,13 @@ class KVCache:
         k = qkv[:, :, H * D:(H + Hkv) * D]
         if rope is not None:
             k = ops.rope_(k.contiguous(), rope[0], rope[1], Hkv, D)
+        v = qkv[:, :, (H + Hkv) * D:]
+        if self.is_fp8:  # once per prompt: a clamp and a cast (the decode kernel quantises its own row)
+            from .ops.decode import q8
+
+            k, v = q8(k), q8(v)
         self.k[layer, :, :, :T] = k.reshape(B, T, Hkv, D).transpose(1, 2)
-        self.v[layer, :, :, :T] = qkv[:, :, (H + Hkv) * D:].reshape(B, T, Hkv, D).transpose(1, 2)
+        self.v[layer, :, :, :T] = v.reshape(B, T, Hkv, D).transpose(1, 2)
 
     def attend(self, layer: int, qkv: torch.Tensor, pos: torch.Tensor, rope=None, scale=None) -> torch.Tensor:
         """Decode: append the new tokens of ``qkv`` [B, W] at ``pos`` and attend (``ops.decode_attention``)."""
@@ -89,6 +111,9 @@ class KVCache:
         each over the cache up to itself (``ops.append_attention``)."""
         from . import ops
 
+        if self.is_fp8:
+            raise NotImplementedError("KVCache.extend: continuing from an fp8 cache is not implemented "
+                                      "(the block-append kernel reads bf16 caches only)")
         return ops.append_attention(qkv, self.k[layer], self.v[layer], start, nnew, self.n_head, scale=scale,
                                     rope=rope, kv_len_max=self.kv_len_max)
 
@@ -196,6 +221,10 @@ def _continue(model, input_ids, max_new_tokens: int, cache: KVCache, lengths, sa
               pad_token_id: int, graph, sync_every: int):
     """``generate`` from a returned cache: the block ``[cache.pending, turn…]`` per sequence goes
     through ``model.extend`` at ``start = cache.lengths``, then the decode loop takes over."""
+    if cache.is_fp8:
+        # the block-append kernel reads bf16 caches only: refuse before any work
+        raise NotImplementedError("generate: continuing from an fp8 cache (kv_dtype='fp8') is not implemented; "
+                                  "generate the first turn with the default kv_dtype to continue from its cache")
     if max_new_tokens <= 0:
         raise ValueError(f"generate: continuing from a cache needs max_new_tokens >= 1, got {max_new_tokens}")
     if cache.lengths is None or cache.pending is None:
@@ -270,7 +299,7 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
              temperature: float = 0.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
              eos_token_id: Optional[int] = None, pad_token_id: int = 0, graph: Optional[bool] = None,
              t_max: Optional[int] = None, sync_every: int = 32, generator: Optional[torch.Generator] = None,
-             return_cache: bool = False):
+             return_cache: bool = False, kv_dtype=None):
     """Continue each prompt of ``input_ids`` [B, T0] (right-padded; ``lengths`` [B] = prompt
     lengths, default T0) by ``max_new_tokens`` tokens.  Returns [B, T0 + max_new_tokens]: row b
     holds its prompt, then its new tokens from position lengths[b] on, then ``pad_token_id``.
@@ -286,7 +315,14 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
     first call (history + 1 + Tn + max_new_tokens rows).  ``ValueError`` for a cache that no
     ``generate`` call filled, a batch or layout mismatch, too little room, or the model's position
     limit; one host sync (``cache.lengths.max()``).
+
+    ``kv_dtype`` = ``"fp8"`` (or ``torch.float8_e4m3fn``) keeps the KV cache in OCP e4m3 without
+    scales — each row clamped to ±448 and rounded to nearest even from the bf16 row the default
+    cache would hold, by prefill and decode alike — for half the cache bytes held and streamed per
+    token; ``None`` (default) keeps the model's dtype.  A cache of fp8 rows cannot be continued
+    (``cache=`` raises ``NotImplementedError``).
     """
+    kv_dtype = _kv_dtype(kv_dtype)
     if cache is not None:
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator)
         out = _continue(model, input_ids, max_new_tokens, cache, lengths, sampling, eos_token_id, pad_token_id,
@@ -313,7 +349,7 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
         # silently differ from a sliding-window model's (the training forward refuses T > window too)
         raise NotImplementedError(f"generate: {max_len + max_new_tokens} positions exceed the model's "
                                   f"sliding window ({window}); sliding-window decoding is not implemented")
-    cache = KVCache.for_model(model, B, t_max, device=device)
+    cache = KVCache.for_model(model, B, t_max, device=device, dtype=kv_dtype)
     ids = input_ids
     if t_pad > T0:
         ids = torch.cat([ids, torch.full((B, t_pad - T0), pad_token_id, dtype=ids.dtype, device=device)], 1)

@@ -2,6 +2,8 @@
 
 ``csrc/kernels/decode.hip`` on GPU (bf16, head dim 64, up to 8 query heads per key/value head);
 the same math in PyTorch otherwise (CPU, fp32) — also the numerics reference of the GPU tests.
+The caches are bf16 or, with no scales, ``float8_e4m3fn`` (:func:`q8`: half the bytes a decode
+step streams); qkv and the output stay bf16.
 Block append (K17, ``csrc/kernels/append.hip``): several new tokens per sequence at per-sequence
 offsets — what continuing from a returned cache runs instead of a second prefill.
 """
@@ -18,11 +20,29 @@ def partials_numel(batch: int, n_head: int, t_max: int) -> int:
     return batch * n_head * nchunks * 65
 
 
+FP8_MAX = 448.0  # the largest finite float8_e4m3fn (OCP e4m3: no inf)
+
+
+def q8(x):
+    """What an fp8 KV cache holds for a row ``x``: the bf16 row a bf16 cache would hold, clamped to
+    ±448 (so ±inf saturates; NaN stays NaN), rounded to nearest even into ``float8_e4m3fn``.  No
+    scales.  Every e4m3 value is exact in bf16 and fp32, so reading one back rounds nothing."""
+    import torch
+
+    return x.to(torch.bfloat16).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+
+
+def _to_cache(x, dtype):
+    import torch
+
+    return q8(x) if dtype == torch.float8_e4m3fn else x.to(dtype)
+
+
 def decode_supported(qkv, k_cache, n_head: int) -> bool:
     import torch
 
     Hkv = k_cache.shape[1]
-    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_cache.dtype in (torch.bfloat16, torch.float8_e4m3fn)
             and k_cache.shape[-1] == 64 and n_head % Hkv == 0 and n_head // Hkv <= 8)
 
 
@@ -37,7 +57,9 @@ def _rope_at(x, cos, sin, pos):
 
 
 def decode_attention_reference(qkv, k_cache, v_cache, pos, n_head: int, scale: Optional[float] = None, rope=None):
-    """PyTorch version of :func:`decode_attention` (writes the caches the same way)."""
+    """PyTorch version of :func:`decode_attention` (writes the caches the same way).  On fp8 caches
+    the new rows are stored as :func:`q8` makes them and the token attends over the caches as
+    stored, its own row included — as the kernel does."""
     import torch
 
     B, W = qkv.shape
@@ -52,8 +74,8 @@ def decode_attention_reference(qkv, k_cache, v_cache, pos, n_head: int, scale: O
         q = _rope_at(q, rope[0], rope[1], pos)
         k = _rope_at(k, rope[0], rope[1], pos)
     bi = torch.arange(B, device=qkv.device)
-    k_cache[bi, :, pos] = k.to(k_cache.dtype)
-    v_cache[bi, :, pos] = v.to(v_cache.dtype)
+    k_cache[bi, :, pos] = _to_cache(k, k_cache.dtype)
+    v_cache[bi, :, pos] = _to_cache(v, v_cache.dtype)
     mask = torch.arange(Tmax, device=qkv.device)[None, :] > pos[:, None]  # [B, Tmax]
     # rows > pos hold nothing of this sequence (possibly NaN): zeros, and masked below
     held = ~mask[:, None, :, None]
@@ -71,7 +93,8 @@ def decode_attention(qkv, k_cache, v_cache, pos, n_head: int, scale: Optional[fl
     """Attention of one new token per sequence over its KV cache.
 
     ``qkv`` [B, (H + 2·Hkv)·D] is the new tokens' packed projection, ``k_cache``/``v_cache``
-    [B, Hkv, Tmax, D] the caches (rows ≥ ``pos[b]`` are free), ``pos`` int64 [B] the new tokens'
+    [B, Hkv, Tmax, D] the caches (rows ≥ ``pos[b]`` are free; bf16, or ``float8_e4m3fn`` holding
+    :func:`q8` rows: the new rows are then stored quantised and attended as stored), ``pos`` int64 [B] the new tokens'
     positions (on the device: a decode step graph-captures).  The new k (rotated when ``rope`` =
     (cos, sin) tables) and v are written into the caches at ``pos[b]`` and the token attends to
     rows 0..pos[b].  ``kv_len_max`` bounds max(pos) + 1 (default Tmax; smaller = fewer idle
