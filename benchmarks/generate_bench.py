@@ -20,6 +20,15 @@ tokens against the bf16 cache's.
 
     python benchmarks/generate_bench.py --kv-dtype fp8 [--models smollm2,gpt2] [--batches 1,8,32]
         [--prompt 128] [--new 256] [--rounds 7] [--out table.json]
+
+``--shared R``: R samples per prompt over one shared prompt cache (``num_return_sequences=R``)
+against the same call on ``ids.repeat_interleave(R, 0)``: same process, same weights, rounds
+interleaved.  Per (model, batch, prompt): the bytes of both caches, the time to the first token
+(prefill of B against B·R rows) and the marginal ms per token of graphed sampling; per model: the
+decode kernel alone over (prefix, own) against the repeated cache.
+
+    python benchmarks/generate_bench.py --shared 8 [--models smollm2,gpt2] [--batches 4]
+        [--prompts 128,2048] [--new 128] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -229,8 +238,119 @@ def kv_dtype_bench(a):
             json.dump(res, f, indent=1)
 
 
+def shared_kernel_bench(B, R, H, Hkv, Tp, Ts, kv_dtype=torch.bfloat16, n=50, rounds=5):
+    """µs of one layer's decode attention at the last position: ``decode_attention_shared`` over
+    (prefix [B, Hkv, Tp, 64], own [B·R, Hkv, Ts, 64]) and ``decode_attention`` over the repeated
+    cache [B·R, Hkv, Tp + Ts, 64]; rounds of the two interleaved, median and [min, max]."""
+    import statistics
+
+    from nbdistributed_amd import ops
+    from nbdistributed_amd.ops.decode import partials_numel
+
+    S, T = B * R, Tp + Ts
+    mk = lambda *shape: torch.randn(*shape, device="cuda").to(torch.bfloat16).to(kv_dtype)  # noqa: E731
+    pk, pv, ok, ov = mk(B, Hkv, Tp, 64), mk(B, Hkv, Tp, 64), mk(S, Hkv, Ts, 64), mk(S, Hkv, Ts, 64)
+    kc, vc = mk(S, Hkv, T, 64), mk(S, Hkv, T, 64)
+    qkv = torch.randn(S, (H + 2 * Hkv) * 64, device="cuda").to(torch.bfloat16)
+    pos = torch.full((S,), T - 1, device="cuda", dtype=torch.int64)
+    plen = torch.full((B,), Tp, device="cuda", dtype=torch.int64)
+    ws = torch.empty(partials_numel(S, H, T), dtype=torch.float32, device="cuda")
+    arms = {"shared": lambda: ops.decode_attention_shared(qkv, pk, pv, plen, ok, ov, pos, R, H, workspace=ws),
+            "repeated": lambda: ops.decode_attention(qkv, kc, vc, pos, H, workspace=ws)}
+    us = {k: [] for k in arms}
+    for f in arms.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for k, f in arms.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(n):
+                f()
+            e.record()
+            e.synchronize()
+            us[k].append(s.elapsed_time(e) / n * 1e3)
+    r = dict(B=B, R=R, H=H, Hkv=Hkv, Tp=Tp, Ts=Ts, kv_dtype=str(kv_dtype).replace("torch.", ""))
+    for k in arms:
+        r[k + "_us"] = round(statistics.median(us[k]), 2)
+        r[k + "_us_min_max"] = [round(min(us[k]), 2), round(max(us[k]), 2)]
+    r["shared_over_repeated"] = round(r["shared_us"] / r["repeated_us"], 3)
+    r["bytes_addressed"] = dict(shared_distinct=2 * (pk.numel() + ok.numel()) * pk.element_size(),
+                                repeated=2 * kc.numel() * kc.element_size())
+    print(json.dumps(r), flush=True)
+    return r
+
+
+def shared_bench(a):
+    """R samples per prompt over one shared prompt cache against the same call on repeated prompts.
+    The yardstick is the repeated arm of the same run; its own [min, max] is the margin."""
+    import statistics
+
+    from nbdistributed_amd.generation import generate
+
+    R = a.shared
+    res = {"what": f"generate(num_return_sequences={R}) over one shared prompt cache vs the same call on "
+                   f"ids.repeat_interleave({R}, 0): bf16, sampling at temperature 1, graphed decode, rounds interleaved",
+           "R": R, "new_tokens": a.new, "rounds": a.rounds, "points": [], "decode_kernel": []}
+    for name in a.models.split(","):
+        m, vocab, limit, (H, Hkv) = _bench_model(name, a.max_positions)
+        longest = limit - (32 + a.new)
+        prompts = sorted({min(int(x), longest) for x in a.prompts.split(",")})
+        for B in [int(x) for x in a.batches.split(",")]:
+            for prompt in prompts:
+                ids = torch.randint(1, vocab, (B, prompt), device="cuda")
+                rep = ids.repeat_interleave(R, 0)
+                arms = (("shared", lambda n, **kw: generate(m, ids, n, temperature=1.0, graph=True,
+                                                            num_return_sequences=R, **kw)),
+                        ("repeated", lambda n, **kw: generate(m, rep, n, temperature=1.0, graph=True, **kw)))
+                row = dict(model=name, batch=B, R=R, prompt=prompt, prefill_length=m.prefill_length(prompt))
+                ts = {arm: ([], [], []) for arm, _ in arms}
+                for arm, fn in arms:  # warm-up of every length, and the caches
+                    fn(1)
+                    fn(32)
+                    out, cache = fn(32 + a.new, return_cache=True)
+                    row[arm + "_cache_bytes"] = cache.nbytes
+                    row[arm + "_rows_out"] = out.shape[0]
+                    del cache
+                for _ in range(a.rounds):
+                    for arm, fn in arms:
+                        for n, sink in zip((1, 32, 32 + a.new), ts[arm]):
+                            torch.cuda.synchronize()
+                            t = time.perf_counter()
+                            fn(n)
+                            torch.cuda.synchronize()
+                            sink.append((time.perf_counter() - t) * 1e3)
+                for arm, _ in arms:
+                    first, short, long_ = ts[arm]
+                    per = [(lo - sh) / a.new for sh, lo in zip(short, long_)]
+                    row[arm + "_first_token_ms"] = round(statistics.median(first), 3)
+                    row[arm + "_first_token_ms_min_max"] = [round(min(first), 3), round(max(first), 3)]
+                    row[arm + "_ms_per_token"] = round(statistics.median(per), 4)
+                    row[arm + "_ms_per_token_min_max"] = [round(min(per), 4), round(max(per), 4)]
+                row["cache_bytes_ratio"] = round(row["shared_cache_bytes"] / row["repeated_cache_bytes"], 4)
+                row["first_token_speedup"] = round(row["repeated_first_token_ms"] / row["shared_first_token_ms"], 2)
+                row["shared_over_repeated_ms_per_token"] = round(row["shared_ms_per_token"] / row["repeated_ms_per_token"], 3)
+                print(json.dumps(row), flush=True)
+                res["points"].append(row)
+        for B in [int(x) for x in a.batches.split(",")]:
+            for prompt in prompts:
+                r = shared_kernel_bench(B, R, H, Hkv, m.prefill_length(prompt), 32 + a.new)
+                r["model"] = name
+                res["decode_kernel"].append(r)
+        del m
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--shared", type=int, default=0, metavar="R",
+                    help="R samples per prompt over one shared prompt cache vs repeated prompts: --models, --batches "
+                         "(default 4), --prompts, --new (default 128), --rounds")
+    ap.add_argument("--prompts", default="128,2048", help="--shared: prompt lengths (capped by the model's positions)")
     ap.add_argument("--kv-dtype", dest="kv_dtype", default=None, choices=["fp8"],
                     help="add an fp8 KV-cache arm beside the bf16 arm (same process, same weights): --models, "
                          "--batches, --prompt and the longest history each model allows, --new, --rounds")
@@ -251,6 +371,12 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.shared:
+        if a.batches == "1,8,32":
+            a.batches = "4"
+        if a.new == 256:
+            a.new = 128
+        return shared_bench(a)
     if a.kv_dtype:
         return kv_dtype_bench(a)
     if a.cont:

@@ -30,6 +30,18 @@
 // row, one wave instruction reads 512 contiguous bytes; v_cvt_pk_f32_fp8 unpacks into the same fp32
 // lanes.  The new token's register copy is the stored bytes, so it attends to its own key and
 // value as every later step will read them.
+//
+// A shared prefix (`decode_kernel<G, F8, true>`, op `decode_attn_shared`): several samples of one
+// prompt.  Sequence s of S = B·group belongs to prompt s / group; its logical key j is row j of that
+// prompt's prefix cache [B, Hkv, Tp, 64] for j < plen[s / group] and row j - plen of its own cache
+// [S, Hkv, Ts, 64] from there on, so the prompt is held once and the `group` workgroups of a prompt
+// read the same prefix rows.  Only the address of a key differs (base pointer and row index, chosen
+// per key inside `load`); chunking, lane assignment, partials and the merge run over the logical
+// index as before.  The prefix is never written: plen is clamped to [0, Tp] and pos to
+// [plen, plen + Ts - 1] before anything is addressed, so the new row lands in the own cache.
+// Not done here: one workgroup serving all `group` sequences of a prompt, so that a prefix row is
+// loaded once for group·G queries — it needs another register layout (group·G accumulators per
+// lane) and has no measurement behind it; today the sharing of loads is left to L2 and the MALL.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -62,6 +74,11 @@ struct Params {
   float* part_l;  // [B, H, nchunks]
   int H, Hkv, Tmax, nchunks, chunk;
   float scale2;  // softmax scale · log2(e)
+  // decode_kernel<G, F8, true> only (kc / vc are then the own caches [S, Hkv, Tmax = Ts, 64])
+  const void* kpre;  // [S / group, Hkv, Tp, 64], read only
+  const void* vpre;
+  const int64_t* plen;  // [S / group] valid prefix rows
+  int Tp, group;
 };
 
 template <int CTRL>
@@ -153,11 +170,12 @@ __device__ __forceinline__ void rope_lane(float (&x)[8], const float* cos, const
   }
 }
 
-template <int G, bool F8>
+template <int G, bool F8, bool SHARED>
 __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   // keys in flight per group.  The same on an fp8 cache, though a load is half the bytes: twice
   // the keys measured equal at G = 1, 4-30 % slower at G = 3, 4 and 8 (G = 4, 8: over 256 VGPRs)
-  // and 3 % faster in the one G = 6 shape tried (docs/FINDINGS.md)
+  // and 3 % faster in the one G = 6 shape tried (docs/FINDINGS.md).  The same with SHARED: the two
+  // base pointers and plen cost 0-10 VGPRs, no instantiation spills and none loses a wave
   constexpr int U = G <= 4 ? 4 : 2;
   using row_t = typename Row<F8>::type;
   __shared__ float sm_m[NW][G], sm_l[NW][G];
@@ -168,7 +186,13 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   const int c = blockIdx.x % p.nchunks;
   const int bh = blockIdx.x / p.nchunks;
   const int b = bh / p.Hkv, kvh = bh % p.Hkv;
-  const int pos = (int)min<int64_t>(max<int64_t>(p.pos[b], 0), p.Tmax - 1);
+  // SHARED: keys [0, plen) are prefix rows of prompt b / group, key j >= plen is own row j - plen
+  int plen = 0, pb = 0;
+  if constexpr (SHARED) {
+    pb = b / p.group;
+    plen = (int)min<int64_t>(max<int64_t>(p.plen[pb], 0), p.Tp);
+  }
+  const int pos = (int)min<int64_t>(max<int64_t>(p.pos[b], plen), plen + p.Tmax - 1);
   const int len = pos + 1;
   const int c0 = c * p.chunk;
   const int c1 = min(c0 + p.chunk, len);
@@ -205,8 +229,15 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   row_t* const kbase = static_cast<row_t*>(p.kc) + head_base / 8 + d8;
   row_t* const vbase = static_cast<row_t*>(p.vc) + head_base / 8 + d8;
   if (c0 <= pos && pos < c0 + p.chunk && grp == 0) {  // this chunk owns the new row
-    kbase[(int64_t)pos * 8] = knew;
-    vbase[(int64_t)pos * 8] = vnew;
+    kbase[(int64_t)(pos - plen) * 8] = knew;
+    vbase[(int64_t)(pos - plen) * 8] = vnew;
+  }
+  const row_t* kpre = nullptr;
+  const row_t* vpre = nullptr;
+  if constexpr (SHARED) {
+    const int64_t pre_base = ((int64_t)pb * p.Hkv + kvh) * p.Tp * D;
+    kpre = static_cast<const row_t*>(p.kpre) + pre_base / 8 + d8;
+    vpre = static_cast<const row_t*>(p.vpre) + pre_base / 8 + d8;
   }
 
   float m[G], l[G], o[G][8];
@@ -229,8 +260,15 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
       for (int u = 0; u < U; ++u) {
         j[u] = c0 + grp + NG * (it * U + u);
         const int jj = j[u] < c1 ? j[u] : c0;  // in-bounds address for a masked key
-        kr[u] = kb[(int64_t)jj * 8];
-        vr[u] = vb[(int64_t)jj * 8];
+        if constexpr (SHARED) {  // jj <= pos: a prefix row below plen <= Tp, else own row jj - plen < Ts
+          const bool pre = jj < plen;
+          const int64_t r = (int64_t)(pre ? jj : jj - plen) * 8;
+          kr[u] = (pre ? kpre : kb)[r];
+          vr[u] = (pre ? vpre : vb)[r];
+        } else {
+          kr[u] = kb[(int64_t)jj * 8];
+          vr[u] = vb[(int64_t)jj * 8];
+        }
       }
     };
     auto compute = [&](const int (&j)[U], row_t (&kr)[U], row_t (&vr)[U]) {
@@ -384,48 +422,84 @@ static void plan(int64_t BHkv, int64_t kv_len, int& nchunks, int& chunk) {
   chunk = (int)ch;
 }
 
-at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                           const at::Tensor& pos, int64_t n_head, double scale, int64_t kv_len_max,
-                           const c10::optional<at::Tensor>& rope_cos, const c10::optional<at::Tensor>& rope_sin,
-                           const at::Tensor& partials) {
+// the operands of decode_attn_shared that decode_attn has not
+struct Shared {
+  const at::Tensor& k_prefix;
+  const at::Tensor& v_prefix;
+  const at::Tensor& plen;
+  int64_t group;
+};
+
+// both ops: `sh` == nullptr is decode_attn (k_cache / v_cache hold every row), else they are the
+// sequences' own rows behind the prompts' prefixes
+static at::Tensor decode_run(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                             const at::Tensor& pos, int64_t n_head, double scale, int64_t kv_len_max,
+                             const c10::optional<at::Tensor>& rope_cos, const c10::optional<at::Tensor>& rope_sin,
+                             const at::Tensor& partials, const Shared* sh) {
+  const char* op = sh ? "decode_attn_shared" : "decode_attn";
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1 &&
                   qkv.stride(0) % 8 == 0 && ((uintptr_t)qkv.data_ptr() & 15) == 0,
-              "decode_attn: qkv must be a bf16 [B, (H + 2·Hkv)·64] GPU view, unit last stride, 16-B aligned rows");
+              op, ": qkv must be a bf16 [B, (H + 2·Hkv)·64] GPU view, unit last stride, 16-B aligned rows");
   const bool f8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
-  if (f8) {
-    TORCH_CHECK(k_cache.is_cuda() && k_cache.is_contiguous() && k_cache.dim() == 4 && k_cache.size(3) == D &&
-                    v_cache.sizes() == k_cache.sizes() && v_cache.scalar_type() == at::kFloat8_e4m3fn &&
-                    v_cache.is_contiguous() && ((uintptr_t)k_cache.data_ptr() & 7) == 0 &&
-                    ((uintptr_t)v_cache.data_ptr() & 7) == 0,
-                "decode_attn: fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, 64], 8-B aligned rows");
-  } else {
-    TORCH_CHECK(k_cache.is_cuda() && k_cache.scalar_type() == at::kBFloat16 && k_cache.is_contiguous() &&
-                    k_cache.dim() == 4 && k_cache.size(3) == D && v_cache.sizes() == k_cache.sizes() &&
-                    v_cache.scalar_type() == at::kBFloat16 && v_cache.is_contiguous() &&
-                    ((uintptr_t)k_cache.data_ptr() & 15) == 0 && ((uintptr_t)v_cache.data_ptr() & 15) == 0,
-                "decode_attn: caches must be contiguous bf16 [B, Hkv, Tmax, 64]");
-  }
+  auto check_caches = [&](const at::Tensor& k, const at::Tensor& v) {
+    if (f8) {
+      TORCH_CHECK(k.is_cuda() && k.is_contiguous() && k.dim() == 4 && k.size(3) == D && v.sizes() == k.sizes() &&
+                      k.scalar_type() == at::kFloat8_e4m3fn && v.scalar_type() == at::kFloat8_e4m3fn &&
+                      v.is_contiguous() && ((uintptr_t)k.data_ptr() & 7) == 0 && ((uintptr_t)v.data_ptr() & 7) == 0,
+                  op, ": fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, 64], 8-B aligned rows");
+    } else {
+      TORCH_CHECK(k.is_cuda() && k.scalar_type() == at::kBFloat16 && k.is_contiguous() && k.dim() == 4 &&
+                      k.size(3) == D && v.sizes() == k.sizes() && v.scalar_type() == at::kBFloat16 &&
+                      v.is_contiguous() && ((uintptr_t)k.data_ptr() & 15) == 0 && ((uintptr_t)v.data_ptr() & 15) == 0,
+                  op, ": caches must be contiguous bf16 [B, Hkv, Tmax, 64]");
+    }
+  };
+  check_caches(k_cache, v_cache);
   const int64_t B = qkv.size(0), Hkv = k_cache.size(1), Tmax = k_cache.size(2), H = n_head;
-  TORCH_CHECK(k_cache.size(0) == B, "decode_attn: cache batch ", k_cache.size(0), " != ", B);
-  TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && H / Hkv <= 8, "decode_attn: need H % Hkv == 0 and H / Hkv <= 8");
-  TORCH_CHECK(qkv.size(1) == (H + 2 * Hkv) * D, "decode_attn: qkv width ", qkv.size(1), " != (H + 2·Hkv)·64");
+  TORCH_CHECK(k_cache.size(0) == B, op, ": cache batch ", k_cache.size(0), " != ", B);
+  TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && H / Hkv <= 8, op, ": need H % Hkv == 0 and H / Hkv <= 8");
+  TORCH_CHECK(qkv.size(1) == (H + 2 * Hkv) * D, op, ": qkv width ", qkv.size(1), " != (H + 2·Hkv)·64");
   TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.is_contiguous() && pos.numel() == B,
-              "decode_attn: pos must be a contiguous int64 [B] GPU tensor");
-  TORCH_CHECK(kv_len_max >= 1 && kv_len_max <= Tmax, "decode_attn: kv_len_max must be in [1, Tmax]");
+              op, ": pos must be a contiguous int64 [B] GPU tensor");
+  int64_t Tp = 0;  // logical keys: Tp prefix rows (decode_attn: none), then the Tmax rows of k_cache
+  if (sh) {
+    TORCH_CHECK(sh->k_prefix.scalar_type() == k_cache.scalar_type() && sh->v_prefix.scalar_type() == k_cache.scalar_type(),
+                op, ": prefix and own caches must have the same dtype (bf16 or float8_e4m3fn)");
+    check_caches(sh->k_prefix, sh->v_prefix);
+    Tp = sh->k_prefix.size(2);
+    TORCH_CHECK(Tmax >= 1, op, ": the own caches need at least one row");
+    TORCH_CHECK(sh->group >= 1 && B % sh->group == 0 && sh->k_prefix.size(0) == B / sh->group &&
+                    sh->k_prefix.size(1) == Hkv,
+                op, ": prefix caches must be [B / group, Hkv, Tp, 64] for qkv [B, ...] (B ", B, ", group ", sh->group,
+                ", prefix batch ", sh->k_prefix.size(0), ")");
+    TORCH_CHECK(sh->plen.is_cuda() && sh->plen.scalar_type() == at::kLong && sh->plen.is_contiguous() &&
+                    sh->plen.numel() == B / sh->group,
+                op, ": plen must be a contiguous int64 [B / group] GPU tensor");
+    TORCH_CHECK(sh->k_prefix.get_device() == qkv.get_device() && sh->v_prefix.get_device() == qkv.get_device() &&
+                    sh->plen.get_device() == qkv.get_device() && k_cache.get_device() == qkv.get_device() &&
+                    v_cache.get_device() == qkv.get_device() && pos.get_device() == qkv.get_device(),
+                op, ": every operand must be on qkv's device");
+    TORCH_CHECK(Tp + Tmax < (1LL << 31), op, ": too many rows");
+    TORCH_CHECK(kv_len_max >= 1 && kv_len_max <= Tp + Tmax, op, ": kv_len_max must be in [1, Tp + Ts]");
+  } else {
+    TORCH_CHECK(kv_len_max >= 1 && kv_len_max <= Tmax, op, ": kv_len_max must be in [1, Tmax]");
+  }
   const bool hc = rope_cos.has_value() && rope_cos->defined(), hs = rope_sin.has_value() && rope_sin->defined();
-  TORCH_CHECK(hc == hs, "decode_attn: rope_cos and rope_sin go together");
+  TORCH_CHECK(hc == hs, op, ": rope_cos and rope_sin go together");
   if (hc)
     TORCH_CHECK(rope_cos->is_cuda() && rope_cos->scalar_type() == at::kFloat && rope_cos->is_contiguous() &&
-                    rope_cos->dim() == 2 && rope_cos->size(1) == D / 2 && rope_cos->size(0) >= Tmax &&
+                    rope_cos->dim() == 2 && rope_cos->size(1) == D / 2 && rope_cos->size(0) >= Tp + Tmax &&
                     rope_sin->sizes() == rope_cos->sizes() && rope_sin->is_contiguous() &&
                     rope_sin->scalar_type() == at::kFloat,
-                "decode_attn: rope tables must be contiguous float32 [>= Tmax, 32]");
+                op, sh ? ": rope tables must be contiguous float32 [>= Tp + Ts, 32]"
+                       : ": rope tables must be contiguous float32 [>= Tmax, 32]");
   int nchunks, chunk;
   plan(B * Hkv, kv_len_max, nchunks, chunk);
   TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat && partials.is_contiguous() &&
                   partials.numel() >= B * H * nchunks * (D + 1),
-              "decode_attn: partials too small: need ", B * H * nchunks * (D + 1), " floats");
-  TORCH_CHECK(B * Hkv * nchunks < (1LL << 31) && Tmax * D * B * Hkv < (1LL << 62), "decode_attn: grid too large");
+              op, ": partials too small: need ", B * H * nchunks * (D + 1), " floats");
+  TORCH_CHECK(B * Hkv * nchunks < (1LL << 31) && Tmax * D * B * Hkv < (1LL << 62) && Tp * D * B * Hkv < (1LL << 62),
+              op, ": grid too large");
   at::Tensor out = at::empty({B, H * D}, qkv.options().memory_format(at::MemoryFormat::Contiguous));
   Params p;
   p.qkv = static_cast<const uint16_t*>(qkv.data_ptr());
@@ -444,16 +518,28 @@ at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
   p.nchunks = nchunks;
   p.chunk = chunk;
   p.scale2 = (float)scale * kLog2e;
+  p.kpre = sh ? sh->k_prefix.data_ptr() : nullptr;
+  p.vpre = sh ? sh->v_prefix.data_ptr() : nullptr;
+  p.plen = sh ? sh->plen.data_ptr<int64_t>() : nullptr;
+  p.Tp = (int)Tp;
+  p.group = sh ? (int)sh->group : 1;
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
   hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   const dim3 grid((unsigned)(B * Hkv * nchunks));
   switch (H / Hkv) {
-#define NBD_DECODE_G(g)                                                        \
-  case g:                                                                      \
-    if (f8)                                                                    \
-      hipLaunchKernelGGL((decode_kernel<g, true>), grid, dim3(NT), 0, st, p);  \
-    else                                                                       \
-      hipLaunchKernelGGL((decode_kernel<g, false>), grid, dim3(NT), 0, st, p); \
+#define NBD_DECODE_GFS(g, f, s) hipLaunchKernelGGL((decode_kernel<g, f, s>), grid, dim3(NT), 0, st, p)
+#define NBD_DECODE_G(g)                    \
+  case g:                                  \
+    if (sh) {                              \
+      if (f8)                              \
+        NBD_DECODE_GFS(g, true, true);     \
+      else                                 \
+        NBD_DECODE_GFS(g, false, true);    \
+    } else if (f8) {                       \
+      NBD_DECODE_GFS(g, true, false);      \
+    } else {                               \
+      NBD_DECODE_GFS(g, false, false);     \
+    }                                      \
     break;
     NBD_DECODE_G(1)
     NBD_DECODE_G(2)
@@ -464,6 +550,7 @@ at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
     NBD_DECODE_G(7)
     NBD_DECODE_G(8)
 #undef NBD_DECODE_G
+#undef NBD_DECODE_GFS
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
   if (nchunks > 1) {
@@ -471,6 +558,24 @@ at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return out;
+}
+
+at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                           const at::Tensor& pos, int64_t n_head, double scale, int64_t kv_len_max,
+                           const c10::optional<at::Tensor>& rope_cos, const c10::optional<at::Tensor>& rope_sin,
+                           const at::Tensor& partials) {
+  return decode_run(qkv, k_cache, v_cache, pos, n_head, scale, kv_len_max, rope_cos, rope_sin, partials, nullptr);
+}
+
+// sequence s of qkv [S = B·group, ...] reads k_prefix / v_prefix [B, Hkv, Tp, 64] rows [0, plen[s / group]) and
+// its own rows k_own / v_own [S, Hkv, Ts, 64]; pos [S] are absolute positions, kv_len_max <= Tp + Ts
+at::Tensor decode_attn_shared_hip(const at::Tensor& qkv, const at::Tensor& k_prefix, const at::Tensor& v_prefix,
+                                  const at::Tensor& plen, const at::Tensor& k_own, const at::Tensor& v_own,
+                                  const at::Tensor& pos, int64_t group, int64_t n_head, double scale,
+                                  int64_t kv_len_max, const c10::optional<at::Tensor>& rope_cos,
+                                  const c10::optional<at::Tensor>& rope_sin, const at::Tensor& partials) {
+  const Shared sh{k_prefix, v_prefix, plen, group};
+  return decode_run(qkv, k_own, v_own, pos, n_head, scale, kv_len_max, rope_cos, rope_sin, partials, &sh);
 }
 
 // ============================================================================ greedy advance
@@ -560,5 +665,6 @@ void greedy_advance_hip(const at::Tensor& logits, const at::Tensor& tok, const a
 
 TORCH_LIBRARY_IMPL(nbd, CUDA, m) {
   m.impl("decode_attn", &nbd::decode::decode_attn_hip);
+  m.impl("decode_attn_shared", &nbd::decode::decode_attn_shared_hip);
   m.impl("greedy_advance", &nbd::decode::greedy_advance_hip);
 }

@@ -23,6 +23,10 @@ TORCH_LIBRARY(nbd, m) {
         "Tensor qend) -> ()");
   m.def("decode_attn(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor pos, int n_head, float scale, "
         "int kv_len_max, Tensor? rope_cos, Tensor? rope_sin, Tensor(c!) partials) -> Tensor");
+  // several samples per prompt: sequence s of S = B·group reads prompt s / group's prefix rows [0, plen), then its own
+  m.def("decode_attn_shared(Tensor qkv, Tensor k_prefix, Tensor v_prefix, Tensor plen, Tensor(a!) k_own, "
+        "Tensor(b!) v_own, Tensor pos, int group, int n_head, float scale, int kv_len_max, Tensor? rope_cos, "
+        "Tensor? rope_sin, Tensor partials) -> Tensor");
   // a block of new tokens per sequence over the cache (csrc/kernels/append.hip): k | v appended at start[b] + i
   m.def("append_attn(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor start, Tensor nnew, int n_head, "
         "float scale, int kv_len_max, Tensor? rope_cos, Tensor? rope_sin) -> Tensor");

@@ -19,7 +19,11 @@ The reference's notebooks train; after training, a user of an interactive notebo
   cache); ``generate(turn, n, cache=cache)`` runs only ``[pending, turn…]`` through the stack,
   with ``ops.append_attention`` (``csrc/kernels/append.hip``) attending the block over the cache
   at per-sequence offsets and appending it, then enters the same decode loop — no second prefill
-  of the history.
+  of the history;
+* **several samples per prompt** — ``generate(..., num_return_sequences=R)`` prefills the B
+  prompts once into a ``SharedPrefixKVCache`` (each prompt held once, R short tails of own rows)
+  and decodes B·R sequences with ``ops.decode_attention_shared``: the same decode kernel, a key's
+  address taken from the prompt's prefix or the sample's own rows.
 
 Models opt in by providing ``kv_layout()``, ``prefill(ids, cache, lengths)``,
 ``decode_step(tok, pos, cache)`` and ``extend(ids, cache, start, nnew)``; see ``models/gpt2.py``
@@ -118,6 +122,73 @@ class KVCache:
                                     rope=rope, kv_len_max=self.kv_len_max)
 
 
+class SharedPrefixKVCache:
+    """The cache of ``generate(..., num_return_sequences=R)``: ``prompts`` prompts held once, in
+    prefix tensors ``k`` / ``v`` [n_layer, prompts, Hkv, t_prefix, D], and ``group`` = R samples of
+    each with their own rows ``k_own`` / ``v_own`` [n_layer, prompts·group, Hkv, t_own, D].
+    Sequence s (a sample) belongs to prompt s // group; its position j is prefix row j below
+    ``plen[s // group]`` (the prompt's length, int64 [prompts] on the device) and own row
+    j - plen from there on.  The surface the models use is ``KVCache``'s: ``t_max`` (the absolute
+    capacity t_prefix + t_own: RoPE tables are sized from it), ``store`` (prefill, into the prefix)
+    and ``attend`` (decode, ``ops.decode_attention_shared``).  It cannot be continued."""
+
+    def __init__(self, n_layer: int, prompts: int, group: int, n_head: int, n_kv: int, t_prefix: int, t_own: int,
+                 head_dim: int, dtype=torch.bfloat16, device="cuda"):
+        if group < 1 or t_own < 1:
+            raise ValueError(f"SharedPrefixKVCache: need group >= 1 and t_own >= 1, got {group}, {t_own}")
+        self.n_layer, self.prompts, self.group, self.n_head, self.n_kv, self.head_dim = (
+            n_layer, prompts, group, n_head, n_kv, head_dim)
+        self.batch = prompts * group  # sequences, as the decode loop counts them
+        self.t_prefix, self.t_own, self.t_max = t_prefix, t_own, t_prefix + t_own
+        self.k = torch.zeros((n_layer, prompts, n_kv, t_prefix, head_dim), dtype=dtype, device=device)
+        self.v = torch.zeros_like(self.k)
+        self.k_own = torch.zeros((n_layer, self.batch, n_kv, t_own, head_dim), dtype=dtype, device=device)
+        self.v_own = torch.zeros_like(self.k_own)
+        self.plen = torch.zeros(prompts, dtype=torch.int64, device=device)  # valid prefix rows per prompt
+        from .ops.decode import partials_numel
+
+        self.workspace = torch.empty(partials_numel(self.batch, n_head, self.t_max), dtype=torch.float32, device=device)
+        self.kv_len_max: Optional[int] = None  # host bound on max(pos) + 1 (None = t_max)
+        self.lengths: Optional[torch.Tensor] = None  # int64 [prompts·group]: valid positions per sequence
+        self.pending: Optional[torch.Tensor] = None  # the last emitted token of each, not yet in the cache
+
+    @classmethod
+    def for_model(cls, model, prompts: int, group: int, t_prefix: int, t_own: int, device=None,
+                  dtype=None) -> "SharedPrefixKVCache":
+        L, H, Hkv, D = model.kv_layout()
+        p = next(model.parameters())
+        return cls(L, prompts, group, H, Hkv, t_prefix, t_own, D, dtype=dtype or p.dtype, device=device or p.device)
+
+    @property
+    def nbytes(self) -> int:
+        return 2 * (self.k.numel() + self.k_own.numel()) * self.k.element_size()
+
+    @property
+    def is_fp8(self) -> bool:
+        return self.k.dtype == torch.float8_e4m3fn
+
+    def store(self, layer: int, qkv: torch.Tensor, rope=None) -> None:
+        """Prefill: k (rotated by ``rope``) and v of the prompts' packed [prompts, T, W] projection
+        into prefix rows [0, T) of ``layer`` (``KVCache.store``'s rule, fp8 included)."""
+        if qkv.shape[0] != self.prompts or qkv.shape[1] > self.t_prefix:
+            raise ValueError(f"SharedPrefixKVCache.store: a [{qkv.shape[0]}, {qkv.shape[1]}, ...] projection does "
+                             f"not fit {self.prompts} prefixes of {self.t_prefix} rows")
+        KVCache.store(self, layer, qkv, rope)
+
+    def attend(self, layer: int, qkv: torch.Tensor, pos: torch.Tensor, rope=None, scale=None) -> torch.Tensor:
+        """Decode: append the new tokens of ``qkv`` [prompts·group, W] at absolute positions ``pos``
+        to their own rows and attend over prefix + own (``ops.decode_attention_shared``)."""
+        from . import ops
+
+        return ops.decode_attention_shared(qkv, self.k[layer], self.v[layer], self.plen, self.k_own[layer],
+                                           self.v_own[layer], pos, self.group, self.n_head, scale=scale, rope=rope,
+                                           kv_len_max=self.kv_len_max, workspace=self.workspace)
+
+    def extend(self, *args, **kwargs):
+        raise NotImplementedError("SharedPrefixKVCache.extend: continuing from a shared-prefix cache is not "
+                                  "implemented (the block-append kernel reads one cache per sequence)")
+
+
 def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: Optional[int] = None,
            top_p: Optional[float] = None, generator: Optional[torch.Generator] = None) -> torch.Tensor:
     """Next tokens [B] from logits [B, V]: greedy at ``temperature`` 0, else a softmax sample
@@ -143,7 +214,7 @@ def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: Optional[int] 
 class _DecodeLoop:
     """One decode step (model step + sampling + bookkeeping) on static buffers; eager or graphed."""
 
-    def __init__(self, model, cache: KVCache, tok, pos, out, done, eos: Optional[int], sampling: dict):
+    def __init__(self, model, cache, tok, pos, out, done, eos: Optional[int], sampling: dict):
         self.model, self.cache = model, cache
         self.tok, self.pos, self.out, self.done, self.eos = tok, pos, out, done, eos
         self.sampling = sampling
@@ -293,13 +364,62 @@ def _continue(model, input_ids, max_new_tokens: int, cache: KVCache, lengths, sa
     return out
 
 
+def _generate_shared(model, input_ids, max_new_tokens: int, R: int, lengths, sampling: dict, eos_token_id,
+                     pad_token_id: int, graph, t_max, sync_every: int, kv_dtype):
+    """``generate`` with ``num_return_sequences`` = R > 1: one prefill of the B prompts into the prefix
+    of a ``SharedPrefixKVCache``, then the decode loop over B·R sequences.  Returns (out, cache)."""
+    device = input_ids.device
+    B, T0 = input_ids.shape
+    if max_new_tokens <= 0:
+        return input_ids.repeat_interleave(R, 0), None
+    lens = (torch.full((B,), T0, dtype=torch.int64, device=device) if lengths is None
+            else lengths.to(device=device, dtype=torch.int64))
+    max_len = int(lens.max())  # one host sync, before any decoding
+    if int(lens.min()) < 1:
+        raise ValueError("generate: every prompt needs at least one token")
+    t_pad = model.prefill_length(T0)
+    need = max(t_pad, max_len + max_new_tokens)
+    t_max = t_max or need
+    limit = model.max_positions()
+    if t_max < need or (limit is not None and need > limit):
+        raise ValueError(f"generate: needs {need} positions (t_max {t_max}, model limit {limit})")
+    window = getattr(getattr(model, "config", None), "sliding_window", None)
+    if window is not None and max_len + max_new_tokens > window:
+        raise NotImplementedError(f"generate: {max_len + max_new_tokens} positions exceed the model's "
+                                  f"sliding window ({window}); sliding-window decoding is not implemented")
+    # the prefix holds the prefill's rows, a sample's own rows its new tokens; t_max= is a floor on the sum
+    cache = SharedPrefixKVCache.for_model(model, B, R, t_pad, max(max_new_tokens, t_max - t_pad), device=device,
+                                          dtype=kv_dtype)
+    ids = input_ids
+    if t_pad > T0:
+        ids = torch.cat([ids, torch.full((B, t_pad - T0), pad_token_id, dtype=ids.dtype, device=device)], 1)
+    logits = model.prefill(ids, cache, lens)
+    cache.plen.copy_(lens)
+    # the draws have the shape [B·R, V] of the same call on repeated prompts: the same tokens for a seed
+    tok = sample(logits.repeat_interleave(R, 0), **sampling)
+    out = torch.full((B, T0 + max_new_tokens), pad_token_id, dtype=input_ids.dtype, device=device)
+    out[:, :T0] = input_ids
+    ar = torch.arange(T0, device=device)
+    out[:, :T0].masked_fill_(ar[None, :] >= lens[:, None], pad_token_id)
+    out = out.repeat_interleave(R, 0)
+    pos = lens.repeat_interleave(R)  # position of `tok`
+    out.scatter_(1, pos.view(-1, 1), tok.view(-1, 1))
+    done = ((tok == eos_token_id) if eos_token_id is not None
+            else torch.zeros(B * R, dtype=torch.bool, device=device))
+    if graph is None:
+        graph = device.type == "cuda" and sampling["generator"] is None
+    loop = _DecodeLoop(model, cache, tok, pos, out, done, eos_token_id, sampling)
+    _run_decode(loop, max_new_tokens - 1, graph, max_len + 1, eos_token_id, sync_every)
+    return out, cache
+
+
 @torch.no_grad()
 def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
              lengths: Optional[torch.Tensor] = None, cache: Optional[KVCache] = None,
              temperature: float = 0.0, top_k: Optional[int] = None, top_p: Optional[float] = None,
              eos_token_id: Optional[int] = None, pad_token_id: int = 0, graph: Optional[bool] = None,
              t_max: Optional[int] = None, sync_every: int = 32, generator: Optional[torch.Generator] = None,
-             return_cache: bool = False, kv_dtype=None):
+             return_cache: bool = False, kv_dtype=None, num_return_sequences: int = 1):
     """Continue each prompt of ``input_ids`` [B, T0] (right-padded; ``lengths`` [B] = prompt
     lengths, default T0) by ``max_new_tokens`` tokens.  Returns [B, T0 + max_new_tokens]: row b
     holds its prompt, then its new tokens from position lengths[b] on, then ``pad_token_id``.
@@ -321,8 +441,32 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
     cache would hold, by prefill and decode alike — for half the cache bytes held and streamed per
     token; ``None`` (default) keeps the model's dtype.  A cache of fp8 rows cannot be continued
     (``cache=`` raises ``NotImplementedError``).
+
+    ``num_return_sequences`` = R > 1 draws R samples of every prompt (``temperature`` > 0): the B
+    prompts are prefilled once into a ``SharedPrefixKVCache`` that holds each prompt once and R
+    short tails, and the decode loop runs at batch B·R with ``ops.decode_attention_shared``.  The
+    result is [B·R, T0 + max_new_tokens], row b·R + r laid out as above; the tokens are those of
+    the same call on ``input_ids.repeat_interleave(R, 0)`` with the same ``generator``.  The
+    returned cache is the shared one, and cannot be continued (``cache=`` raises
+    ``NotImplementedError``); R > 1 together with ``cache=`` or greedy decoding is a ``ValueError``.
     """
     kv_dtype = _kv_dtype(kv_dtype)
+    R = int(num_return_sequences)
+    if R < 1:
+        raise ValueError(f"generate: num_return_sequences must be >= 1, got {num_return_sequences}")
+    if cache is not None and R > 1:
+        raise ValueError("generate: num_return_sequences > 1 starts from prompts, not from cache=")
+    if isinstance(cache, SharedPrefixKVCache):
+        raise NotImplementedError("generate: continuing from a shared prefix cache (num_return_sequences > 1) is "
+                                  "not implemented")
+    if R > 1:
+        if temperature <= 0.0:
+            raise ValueError("generate: num_return_sequences > 1 needs temperature > 0 (greedy samples of one "
+                             "prompt are copies of each other)")
+        sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator)
+        out, shared = _generate_shared(model, input_ids, max_new_tokens, R, lengths, sampling, eos_token_id,
+                                       pad_token_id, graph, t_max, sync_every, kv_dtype)
+        return (out, shared) if return_cache else out
     if cache is not None:
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator)
         out = _continue(model, input_ids, max_new_tokens, cache, lengths, sampling, eos_token_id, pad_token_id,
@@ -370,4 +514,4 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
     return (out, cache) if return_cache else out
 
 
-__all__ = ["KVCache", "generate", "sample"]
+__all__ = ["KVCache", "SharedPrefixKVCache", "generate", "sample"]

@@ -27,6 +27,8 @@ mlp_gelu /             + bias / GELU / GELU' / SwiGLU / SwiGLU'          swizzle
 mlp_swiglu (K12)       epilogues, split-K, K-groups
 decode_attention (K13) one-token attention over a KV cache: RoPE +      decode.hip (split keys,
                        cache append + softmax·V + chunk merge           merge kernel)
+decode_attention_      the same over a prompt's shared prefix rows plus  decode.hip (decode_kernel
+shared (K13)           the sample's own rows (several samples / prompt)  <G, F8, SHARED>)
 linear_small (K14)     decode linear: LN/RMS prologue + x·Wᵀ (MFMA) +   smallm.hip
                        bias / GELU / SwiGLU / residual epilogue, M ≤ 64
 packed_bounds (K16)    position_ids of packed rows -> per-query start /  packed.hip (one wave per
@@ -51,7 +53,8 @@ from . import graddst
 from .bucket import (_ref_flatten, _ref_prereduce, _ref_unflatten, bucket_flatten, bucket_unflatten, local_prereduce,
                      plan_offsets, prereduce_into_bucket)
 from .decode import (append_attention, append_attention_reference, append_supported, decode_attention,
-                     decode_attention_reference, linear_small, linear_small_reference)
+                     decode_attention_reference, decode_attention_shared, decode_attention_shared_reference,
+                     linear_small, linear_small_reference)
 from .embedding import embedding, embedding_tok_pos
 from .gemm import (block_graphs, block_graphs_memory, block_graphs_reset, block_graphs_stats, cast_buffers_memory,
                    gemm_linear, llama_block, mlp_gelu, mlp_swiglu)
@@ -71,7 +74,7 @@ def __getattr__(name):
 
 
 __all__ = ["linear_tiny", "bucket_flatten", "bucket_unflatten", "local_prereduce", "prereduce_into_bucket", "graddst", "adamw_flat", "cross_entropy", "linear_cross_entropy",
-           "flash_attention", "attention_qkv", "decode_attention", "decode_attention_reference", "append_attention", "append_attention_reference", "append_supported", "linear_small", "linear_small_reference", "flash_supported", "layer_norm", "add_layer_norm", "linear",
+           "flash_attention", "attention_qkv", "decode_attention", "decode_attention_reference", "decode_attention_shared", "decode_attention_shared_reference", "append_attention", "append_attention_reference", "append_supported", "linear_small", "linear_small_reference", "flash_supported", "layer_norm", "add_layer_norm", "linear",
            "colsum", "embedding", "embedding_tok_pos", "gemm_linear", "llama_block", "block_graphs", "block_graphs_memory", "block_graphs_reset", "block_graphs_stats", "cast_buffers_memory", "mlp_gelu", "mlp_swiglu", "rms_norm", "add_rms_norm", "embed_rms_norm", "tokpos_layer_norm", "rope_", "rope_tables", "swiglu", "tensor_summary",
            "tensor_summary_text", "tensor_summary_raw", "plan_offsets", "native_available", "load_library",
            "SUMMARY_FIELDS", "seqcls_prep", "packed_bounds", "PackedBounds"]

@@ -4,6 +4,8 @@
 the same math in PyTorch otherwise (CPU, fp32) — also the numerics reference of the GPU tests.
 The caches are bf16 or, with no scales, ``float8_e4m3fn`` (:func:`q8`: half the bytes a decode
 step streams); qkv and the output stay bf16.
+Shared prefix (``decode_attention_shared``): ``group`` consecutive sequences read one prompt's prefix
+rows and then their own — several samples per prompt with the prompt held once.
 Block append (K17, ``csrc/kernels/append.hip``): several new tokens per sequence at per-sequence
 offsets — what continuing from a returned cache runs instead of a second prefill.
 """
@@ -115,6 +117,105 @@ def decode_attention(qkv, k_cache, v_cache, pos, n_head: int, scale: Optional[fl
         return torch.ops.nbd.decode_attn(qkv, k_cache, v_cache, pos, int(n_head), sc, int(kv_len_max or Tmax),
                                          cos, sin, workspace)
     return decode_attention_reference(qkv, k_cache, v_cache, pos, n_head, sc, rope)
+
+
+# ------------------------------------------------------------------ shared prefix (several samples per prompt)
+def decode_shared_supported(qkv, k_prefix, k_own, n_head: int) -> bool:
+    import torch
+
+    Hkv = k_own.shape[1]
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_own.dtype in (torch.bfloat16, torch.float8_e4m3fn)
+            and k_prefix.dtype == k_own.dtype and k_own.shape[-1] == 64 and k_prefix.shape[-1] == 64
+            and n_head % Hkv == 0 and n_head // Hkv <= 8)
+
+
+def _shared_span(plen, pos, group: int, Tp: int, Ts: int):
+    """``plen`` [B] and ``pos`` [B·group] clamped as the kernel clamps them before addressing:
+    0 ≤ plen ≤ Tp, then plen ≤ pos ≤ plen + Ts - 1 (the new row never lands in the prefix).
+    Returns (plen per sequence [B·group], pos)."""
+    import torch
+
+    pl = plen.long().clamp(0, Tp).repeat_interleave(group)
+    pos = torch.minimum(torch.maximum(pos.long(), pl), pl + (Ts - 1))
+    return pl, pos
+
+
+def decode_attention_shared_reference(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, group: int, n_head: int,
+                                      scale: Optional[float] = None, rope=None):
+    """PyTorch version of :func:`decode_attention_shared` (writes the own caches the same way, never
+    the prefix).  On fp8 caches the new rows are stored as :func:`q8` makes them and the token
+    attends over the caches as stored, its own row included — as the kernel does."""
+    import torch
+
+    S, W = qkv.shape
+    Hkv, Ts, D = k_own.shape[1], k_own.shape[2], k_own.shape[3]
+    Tp = k_prefix.shape[2]
+    H, G = n_head, n_head // Hkv
+    dev = qkv.device
+    sc = float(scale) if scale is not None else D ** -0.5
+    pl, pos = _shared_span(plen, pos, group, Tp, Ts)
+    q = qkv[:, : H * D].view(S, H, D)
+    k = qkv[:, H * D:(H + Hkv) * D].view(S, Hkv, D)
+    v = qkv[:, (H + Hkv) * D:].view(S, Hkv, D)
+    if rope is not None:
+        q = _rope_at(q, rope[0], rope[1], pos)
+        k = _rope_at(k, rope[0], rope[1], pos)
+    si = torch.arange(S, device=dev)
+    k_own[si, :, pos - pl] = _to_cache(k, k_own.dtype)
+    v_own[si, :, pos - pl] = _to_cache(v, v_own.dtype)
+    # logical key j of sequence s: prefix[s // group, :, j] below plen, own[s, :, j - plen] from there on
+    j = torch.arange(Tp + Ts, device=dev)[None, :]  # [1, Tp + Ts]
+    in_pre = j < pl[:, None]  # [S, T]
+    mask = j > pos[:, None]
+    held = (~mask)[:, None, :, None]
+    zero = torch.zeros((), device=dev)
+
+    def logical(pre, own):
+        # rows > pos hold nothing of this sequence (possibly NaN): zeros, and masked below
+        a = pre.float()[si // group][:, :, j[0].clamp(max=max(Tp - 1, 0))] if Tp else None
+        b = own.float()[si[:, None], :, (j - pl[:, None]).clamp(0, Ts - 1)].transpose(1, 2)  # [S, Hkv, T, D]
+        m = b if a is None else torch.where(in_pre[:, None, :, None], a, b)
+        return torch.where(held, m, zero)
+
+    kc, vc = logical(k_prefix, k_own), logical(v_prefix, v_own)
+    s = torch.einsum("bkgd,bktd->bkgt", q.float().view(S, Hkv, G, D), kc) * sc
+    s = s.masked_fill(mask[:, None, None, :], float("-inf"))
+    p = torch.softmax(s, -1)
+    o = torch.einsum("bkgt,bktd->bkgd", p, vc)
+    return o.reshape(S, H * D).to(qkv.dtype)
+
+
+def decode_attention_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, group: int, n_head: int,
+                            scale: Optional[float] = None, rope=None, kv_len_max: Optional[int] = None,
+                            workspace=None):
+    """Attention of one new token per sequence where ``group`` consecutive sequences share a prompt.
+
+    ``qkv`` [S = B·group, (H + 2·Hkv)·D]; sequence s belongs to prompt s // group.  Its logical key
+    j is ``k_prefix[s // group, :, j]`` ([B, Hkv, Tp, D], read only) for j < ``plen[s // group]``
+    (int64 [B] on the device) and ``k_own[s, :, j - plen]`` ([S, Hkv, Ts, D]) from there on.
+    ``pos`` int64 [S] are absolute positions: the new k (rotated at ``pos``) and v are written to
+    own row ``pos - plen`` and the token attends logical keys 0..pos.  ``plen`` is clamped to
+    [0, Tp] and ``pos`` to [plen, plen + Ts - 1] first.  ``kv_len_max`` bounds max(pos) + 1 (default
+    Tp + Ts); ``workspace`` as in :func:`decode_attention`, sized for S sequences and Tp + Ts keys.
+    bf16 or ``float8_e4m3fn`` caches (prefix and own alike).  Returns [S, H·D]."""
+    import torch
+
+    D = k_own.shape[-1]
+    sc = float(scale) if scale is not None else D ** -0.5
+    if k_prefix.dtype != k_own.dtype or v_prefix.dtype != k_own.dtype or v_own.dtype != k_own.dtype:
+        raise ValueError(f"decode_attention_shared: prefix ({k_prefix.dtype}) and own ({k_own.dtype}) caches "
+                         f"must have the same dtype")
+    if decode_shared_supported(qkv, k_prefix, k_own, n_head):
+        _require()
+        S, T = k_own.shape[0], k_prefix.shape[2] + k_own.shape[2]
+        if workspace is None:
+            workspace = torch.empty(partials_numel(S, n_head, T), dtype=torch.float32, device=qkv.device)
+        cos, sin = rope if rope is not None else (None, None)
+        if qkv.stride(-1) != 1 or qkv.stride(0) % 8 or qkv.data_ptr() % 16:
+            qkv = qkv.contiguous()
+        return torch.ops.nbd.decode_attn_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, int(group),
+                                                int(n_head), sc, int(kv_len_max or T), cos, sin, workspace)
+    return decode_attention_shared_reference(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, group, n_head, sc, rope)
 
 
 # ------------------------------------------------------------------ block append (K17)
