@@ -29,6 +29,16 @@ decode kernel alone over (prefix, own) against the repeated cache.
 
     python benchmarks/generate_bench.py --shared 8 [--models smollm2,gpt2] [--batches 4]
         [--prompts 128,2048] [--new 128] [--rounds 7] [--out table.json]
+
+``--head-dim 128``: the decode kernel at head dim 128 on a Llama-3.2-3B-shaped stack (hidden 3072, 24
+heads on 8 kv heads of 128, ``--layers`` layers, random bf16 weights).  ms per ``decode_step`` with
+the HIP kernel against the same call with ``ops.decode.decode_supported`` patched to False (the
+PyTorch path these models ran before), bf16 and fp8 caches, at ``--batches`` x ``--hist``; and the
+kernel alone against the 64 kernel at equal streamed bytes (same B, G and kv_len, Hkv = h at 128
+against 2h at 64).  Both arms in one process, rounds interleaved.
+
+    python benchmarks/generate_bench.py --head-dim 128 [--layers 4] [--batches 1,8,32]
+        [--hist 128,4096] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -345,8 +355,110 @@ def shared_bench(a):
             json.dump(res, f, indent=1)
 
 
+def head_dim_bench(a):
+    """Head dim 128 in the decode kernel: a model-level arm against the PyTorch fallback and a
+    kernel-alone arm against the 64 kernel at equal streamed bytes (see the module docstring)."""
+    import contextlib
+    import statistics
+    from unittest import mock
+
+    from nbdistributed_amd import ops
+    from nbdistributed_amd.generation import KVCache
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+    from nbdistributed_amd.ops.decode import partials_numel
+
+    D = a.head_dim
+    med = lambda xs: round(statistics.median(xs), 4)  # noqa: E731
+    span = lambda xs: [round(min(xs), 4), round(max(xs), 4)]  # noqa: E731
+    res = {"what": f"decode attention at head dim {D}: Llama-3.2-3B-shaped stack of {a.layers} layers (hidden 3072, 24 / 8 "
+                   f"heads), random bf16 weights, eager decode_step; HIP kernel vs decode_supported patched to False; "
+                   f"and the kernel alone vs the 64 kernel at equal streamed bytes; rounds interleaved",
+           "layers": a.layers, "rounds": a.rounds, "model": [], "kernel": []}
+    torch.manual_seed(0)
+    cfg = LlamaConfig(vocab_size=32000, hidden_size=3072, intermediate_size=8192, num_hidden_layers=a.layers,
+                      num_attention_heads=24, num_key_value_heads=8, max_position_embeddings=8192, explicit_head_dim=D)
+    m = LlamaForCausalLM(cfg).to("cuda", torch.bfloat16).eval()
+    hists = [int(x) for x in a.hist.split(",")]
+    batches = [int(x) for x in a.batches.split(",")]
+    steps = 8
+    for kv in (torch.bfloat16, torch.float8_e4m3fn):
+        for B in batches:
+            for hist in hists:
+                cache = KVCache.for_model(m, B, hist + 64, dtype=kv)  # a random history: no prefill needed
+                for t in (cache.k, cache.v):
+                    t.copy_(torch.randn(t.shape, device="cuda", dtype=torch.bfloat16).to(kv))
+                tok = torch.randint(1, 32000, (B,), device="cuda")
+                pos = torch.full((B,), hist, device="cuda", dtype=torch.int64)
+
+                def run():
+                    for i in range(steps):
+                        m.decode_step(tok, pos + i, cache)
+
+                ms = {"hip": [], "fallback": []}
+                for _ in range(a.rounds + 1):  # the first round warms up
+                    for arm in ("hip", "fallback"):
+                        with (mock.patch.object(ops.decode, "decode_supported", lambda *x: False) if arm == "fallback"
+                              else contextlib.nullcontext()):
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            run()
+                            torch.cuda.synchronize()
+                            ms[arm].append((time.perf_counter() - t0) * 1e3 / steps)
+                row = dict(kv_dtype=str(kv).replace("torch.", ""), batch=B, history=hist)
+                for arm in ms:
+                    row[arm + "_ms_per_token"], row[arm + "_min_max"] = med(ms[arm][1:]), span(ms[arm][1:])
+                row["fallback_over_hip"] = round(row["fallback_ms_per_token"] / row["hip_ms_per_token"], 2)
+                print(json.dumps(row), flush=True)
+                res["model"].append(row)
+                del cache
+                torch.cuda.empty_cache()
+    del m
+    torch.cuda.empty_cache()
+    # the kernel alone: 128 with Hkv = h against 64 with Hkv = 2h (the same K + V bytes), same B, G, kv_len
+    for kv in (torch.bfloat16, torch.float8_e4m3fn):
+        for B in batches:
+            for T in hists:
+                for G, h in ((3, 8), (1, 8), (4, 8)):
+                    fns = {}
+                    for d, hk in ((D, h), (64, 2 * h)):
+                        H = G * hk
+                        kc = torch.randn(B, hk, T, d, device="cuda").to(torch.bfloat16).to(kv)
+                        vc = torch.randn(B, hk, T, d, device="cuda").to(torch.bfloat16).to(kv)
+                        qkv = torch.randn(B, (H + 2 * hk) * d, device="cuda").to(torch.bfloat16)
+                        p = torch.full((B,), T - 1, device="cuda", dtype=torch.int64)
+                        ws = torch.empty(partials_numel(B, H, T, d), dtype=torch.float32, device="cuda")
+                        fns[d] = (lambda qkv=qkv, kc=kc, vc=vc, p=p, H=H, ws=ws: ops.decode_attention(qkv, kc, vc, p, H, workspace=ws))
+                        for _ in range(3):
+                            fns[d]()
+                    torch.cuda.synchronize()
+                    us = {d: [] for d in fns}
+                    n = 50
+                    for _ in range(a.rounds):
+                        for d, f in fns.items():
+                            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                            s.record()
+                            for _ in range(n):
+                                f()
+                            e.record()
+                            e.synchronize()
+                            us[d].append(s.elapsed_time(e) / n * 1e3)
+                    ratios = [x / y for x, y in zip(us[D], us[64])]
+                    row = dict(kv_dtype=str(kv).replace("torch.", ""), B=B, G=G, kv_len=T, Hkv_128=h, Hkv_64=2 * h,
+                               bytes=2 * B * h * T * D * (1 if kv != torch.bfloat16 else 2),
+                               us_128=round(statistics.median(us[D]), 2), us_64=round(statistics.median(us[64]), 2),
+                               ratio_128_over_64=round(statistics.median(ratios), 3), ratio_min_max=span(ratios))
+                    print(json.dumps(row), flush=True)
+                    res["kernel"].append(row)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--head-dim", dest="head_dim", type=int, default=0, choices=[0, 128],
+                    help="the head-dim-128 decode arm (see the module docstring): --layers, --batches, --hist, --rounds")
+    ap.add_argument("--layers", type=int, default=4, help="--head-dim: layers of the Llama-3.2-3B-shaped stack")
     ap.add_argument("--shared", type=int, default=0, metavar="R",
                     help="R samples per prompt over one shared prompt cache vs repeated prompts: --models, --batches "
                          "(default 4), --prompts, --new (default 128), --rounds")
@@ -371,6 +483,10 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.head_dim:
+        if a.hist == "512,2048,4096":
+            a.hist = "128,4096"
+        return head_dim_bench(a)
     if a.shared:
         if a.batches == "1,8,32":
             a.batches = "4"

@@ -1,6 +1,6 @@
 // decode.hip — single-token (decode) attention over a KV cache for generation, gfx950.
 //
-// One new token per sequence: its packed projection row qkv[b] = [q (H·64) | k (Hkv·64) | v (Hkv·64)]
+// One new token per sequence: its packed projection row qkv[b] = [q (H·D) | k (Hkv·D) | v (Hkv·D)]
 // attends to cache rows 0..pos[b] of its key/value heads, where row pos[b] IS the new token: the
 // kernel writes its (RoPE-rotated) k and v into the cache and uses the register copies for that
 // key, so append + attention are one launch.  The work is pure streaming (each cached key is 256 B
@@ -42,6 +42,15 @@
 // Not done here: one workgroup serving all `group` sequences of a prompt, so that a prefix row is
 // loaded once for group·G queries — it needs another register layout (group·G accumulators per
 // lane) and has no measurement behind it; today the sharing of loads is left to L2 and the MALL.
+//
+// Head dim D = 64 | 128 (`decode_kernel<D, G, F8, SHARED>`, taken from the caches' last dim; the
+// text above describes 64).  A lane holds 8 dims at either width, so the per-lane registers are
+// the same; at 128 a lane group is 16 lanes — one DPP row — and a workgroup has 16 of them: a row
+// is 256 B of bf16 or 128 B of e4m3fn, one wave instruction reads 4 consecutive rows (the same
+// 1 KiB / 512 B), q·k takes one more DPP step (row_mirror) after the 8-lane sum, the RoPE partner
+// dims (±64) sit in lane d8 ^ 8 and the tables are [T, 64], a wave merges 4 groups, and the
+// cross-wave merge and `merge_kernel` run on two waves (thread = dim).  `plan()` is shared: its
+// chunk widths are multiples of 32 groups, hence of 16.
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -55,27 +64,26 @@
 namespace nbd {
 namespace decode {
 
-constexpr int D = 64;
 constexpr int NT = 256;
 constexpr int NW = NT / kWave;  // 4 waves
-constexpr int NG = NT / 8;      // 32 lane groups
+constexpr int NG = NT / 8;      // 32 lane groups at head dim 64 (16 at 128): the unit of plan()'s chunk widths
 constexpr float kLog2e = 1.4426950408889634f;
 
 struct Params {
   const uint16_t* qkv;  // [B, W] bf16 rows (row stride qkv_ld elements)
   int64_t qkv_ld;
-  void* kc;  // [B, Hkv, Tmax, 64] bf16, or e4m3fn (decode_kernel<G, true>)
+  void* kc;  // [B, Hkv, Tmax, D] bf16, or e4m3fn (decode_kernel<D, G, true>)
   void* vc;
   const int64_t* pos;  // [B]
-  const float* cos;    // [>= Tmax, 32] or nullptr
+  const float* cos;    // [>= Tmax, D/2] or nullptr
   const float* sin;
-  uint16_t* out;  // [B, H·64] bf16
-  float* part_o;  // [B, H, nchunks, 64]
+  uint16_t* out;  // [B, H·D] bf16
+  float* part_o;  // [B, H, nchunks, D]
   float* part_l;  // [B, H, nchunks]
   int H, Hkv, Tmax, nchunks, chunk;
   float scale2;  // softmax scale · log2(e)
-  // decode_kernel<G, F8, true> only (kc / vc are then the own caches [S, Hkv, Tmax = Ts, 64])
-  const void* kpre;  // [S / group, Hkv, Tp, 64], read only
+  // decode_kernel<D, G, F8, true> only (kc / vc are then the own caches [S, Hkv, Tmax = Ts, D])
+  const void* kpre;  // [S / group, Hkv, Tp, D], read only
   const void* vpre;
   const int64_t* plen;  // [S / group] valid prefix rows
   int Tp, group;
@@ -94,6 +102,14 @@ __device__ __forceinline__ float sum8(float v) {
   return v;
 }
 
+// sum over the LG = 8 | 16 lanes of a group (16: one DPP row); every lane gets the total
+template <int LG>
+__device__ __forceinline__ float sum_group(float v) {
+  v = sum8(v);
+  if constexpr (LG == 16) v += dpp<0x140>(v);  // row_mirror: lane i <- 15-i, i.e. the other 8 of the 16
+  return v;
+}
+
 __device__ __forceinline__ void unpack8(const u32x4& w, float (&v)[8]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -109,7 +125,7 @@ __device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
   return w;
 }
 
-// a lane's 8 dims of a cache row: 16 B of bf16 or 8 B of e4m3fn; either way a row is 8 of them
+// a lane's 8 dims of a cache row: 16 B of bf16 or 8 B of e4m3fn; either way a row is D/8 of them
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 template <bool F8>
 struct Row {
@@ -155,23 +171,29 @@ __device__ __forceinline__ u32x2 quant8(const u32x4& w) {
   return r;
 }
 
-// HF rotate_half RoPE on this lane's 8 dims [8·d8, 8·d8+8); the partner dims (±32) sit in lane d8^4
+// HF rotate_half RoPE on this lane's 8 dims [8·d8, 8·d8+8); the partner dims (±D/2) sit in lane
+// d8 ^ D/16 (64: d8^4, 128: d8^8); table rows are D/2 floats
+template <int D>
 __device__ __forceinline__ void rope_lane(float (&x)[8], const float* cos, const float* sin, int64_t t, int d8) {
-  const float4* c4 = reinterpret_cast<const float4*>(cos + t * 32 + (d8 & 3) * 8);
-  const float4* s4 = reinterpret_cast<const float4*>(sin + t * 32 + (d8 & 3) * 8);
+  constexpr int HL = D / 16;  // lanes per half row
+  const float4* c4 = reinterpret_cast<const float4*>(cos + t * (D / 2) + (d8 & (HL - 1)) * 8);
+  const float4* s4 = reinterpret_cast<const float4*>(sin + t * (D / 2) + (d8 & (HL - 1)) * 8);
   const float4 ca = c4[0], cb = c4[1], sa = s4[0], sb = s4[1];
   const float c[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
   const float s[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
-  const float sg = d8 < 4 ? -1.f : 1.f;  // x1·c − x2·s  |  x2·c + x1·s
+  const float sg = d8 < HL ? -1.f : 1.f;  // x1·c − x2·s  |  x2·c + x1·s
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    const float y = __shfl_xor(x[e], 4, kWave);
+    const float y = __shfl_xor(x[e], HL, kWave);
     x[e] = x[e] * c[e] + sg * y * s[e];
   }
 }
 
-template <int G, bool F8, bool SHARED>
+template <int D, int G, bool F8, bool SHARED>
 __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
+  static_assert(D == 64 || D == 128, "head dim 64 or 128");
+  constexpr int LG = D / 8;    // lanes per group: a lane holds 8 dims, a group one row
+  constexpr int NGR = NT / LG;  // groups per workgroup: 32 | 16
   // keys in flight per group.  The same on an fp8 cache, though a load is half the bytes: twice
   // the keys measured equal at G = 1, 4-30 % slower at G = 3, 4 and 8 (G = 4, 8: over 256 VGPRs)
   // and 3 % faster in the one G = 6 shape tried (docs/FINDINGS.md).  The same with SHARED: the two
@@ -182,7 +204,7 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   __shared__ float sm_o[NW][G][D];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int grp = tid >> 3, d8 = tid & 7;
+  const int grp = tid >> (LG == 8 ? 3 : 4), d8 = tid & (LG - 1);
   const int c = blockIdx.x % p.nchunks;
   const int bh = blockIdx.x / p.nchunks;
   const int b = bh / p.Hkv, kvh = bh % p.Hkv;
@@ -203,7 +225,7 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     load8<bf16_t>(reinterpret_cast<const bf16_t*>(row + (kvh * G + g) * D + d8 * 8), q[g]);
-    if (p.cos != nullptr) rope_lane(q[g], p.cos, p.sin, pos, d8);
+    if (p.cos != nullptr) rope_lane<D>(q[g], p.cos, p.sin, pos, d8);
 #pragma unroll
     for (int e = 0; e < 8; ++e) q[g][e] *= p.scale2;
   }
@@ -214,7 +236,7 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   {
     float kf[8];
     load8<bf16_t>(reinterpret_cast<const bf16_t*>(row + (p.H + kvh) * D + d8 * 8), kf);
-    if (p.cos != nullptr) rope_lane(kf, p.cos, p.sin, pos, d8);
+    if (p.cos != nullptr) rope_lane<D>(kf, p.cos, p.sin, pos, d8);
     const u32x4 kw = pack8(kf);
     const u32x4 vw = *reinterpret_cast<const u32x4*>(row + (p.H + p.Hkv + kvh) * D + d8 * 8);
     if constexpr (F8) {
@@ -225,12 +247,12 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
       vnew = vw;
     }
   }
-  // a row is 8 row_t (one per lane of a group) in either format
+  // a row is LG row_t (one per lane of a group) in either format
   row_t* const kbase = static_cast<row_t*>(p.kc) + head_base / 8 + d8;
   row_t* const vbase = static_cast<row_t*>(p.vc) + head_base / 8 + d8;
   if (c0 <= pos && pos < c0 + p.chunk && grp == 0) {  // this chunk owns the new row
-    kbase[(int64_t)(pos - plen) * 8] = knew;
-    vbase[(int64_t)(pos - plen) * 8] = vnew;
+    kbase[(int64_t)(pos - plen) * LG] = knew;
+    vbase[(int64_t)(pos - plen) * LG] = vnew;
   }
   const row_t* kpre = nullptr;
   const row_t* vpre = nullptr;
@@ -252,22 +274,22 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   if (c0 < c1) {
     const row_t* kb = kbase;
     const row_t* vb = vbase;
-    const int iters = (c1 - c0 + NG * U - 1) / (NG * U);
+    const int iters = (c1 - c0 + NGR * U - 1) / (NGR * U);
     // two register buffers: the keys / values of iteration it+1 are in flight while iteration it
     // is computed (a chunk is only a few iterations long, so each exposed round trip shows)
     auto load = [&](int it, int (&j)[U], row_t (&kr)[U], row_t (&vr)[U]) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        j[u] = c0 + grp + NG * (it * U + u);
+        j[u] = c0 + grp + NGR * (it * U + u);
         const int jj = j[u] < c1 ? j[u] : c0;  // in-bounds address for a masked key
         if constexpr (SHARED) {  // jj <= pos: a prefix row below plen <= Tp, else own row jj - plen < Ts
           const bool pre = jj < plen;
-          const int64_t r = (int64_t)(pre ? jj : jj - plen) * 8;
+          const int64_t r = (int64_t)(pre ? jj : jj - plen) * LG;
           kr[u] = (pre ? kpre : kb)[r];
           vr[u] = (pre ? vpre : vb)[r];
         } else {
-          kr[u] = kb[(int64_t)jj * 8];
-          vr[u] = vb[(int64_t)jj * 8];
+          kr[u] = kb[(int64_t)jj * LG];
+          vr[u] = vb[(int64_t)jj * LG];
         }
       }
     };
@@ -291,7 +313,7 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
           float acc = 0.f;
 #pragma unroll
           for (int e = 0; e < 8; ++e) acc += q[g][e] * kf[e];
-          acc = sum8(acc);
+          acc = sum_group<LG>(acc);
           s[u][g] = j[u] < c1 ? acc : -INFINITY;
         }
       }
@@ -330,27 +352,27 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
     }
   }
 
-  // merge the 8 groups of this wave (lanes d8, d8+8, …, d8+56)
+  // merge the 64 / LG groups of this wave (lanes d8, d8+LG, …): 8 groups, or 4 (no xor-8 step)
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     float mx = m[g];
-    mx = fmaxf(mx, __shfl_xor(mx, 8, kWave));
+    if constexpr (LG == 8) mx = fmaxf(mx, __shfl_xor(mx, 8, kWave));
     mx = fmaxf(mx, __shfl_xor(mx, 16, kWave));
     mx = fmaxf(mx, __shfl_xor(mx, 32, kWave));
     const float w = mx == -INFINITY ? 0.f : exp2f(m[g] - mx);
     float lg = l[g] * w;
-    lg += __shfl_xor(lg, 8, kWave);
+    if constexpr (LG == 8) lg += __shfl_xor(lg, 8, kWave);
     lg += __shfl_xor(lg, 16, kWave);
     lg += __shfl_xor(lg, 32, kWave);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float x = o[g][e] * w;
-      x += __shfl_xor(x, 8, kWave);
+      if constexpr (LG == 8) x += __shfl_xor(x, 8, kWave);
       x += __shfl_xor(x, 16, kWave);
       x += __shfl_xor(x, 32, kWave);
       o[g][e] = x;
     }
-    if (lane < 8) {
+    if (lane < LG) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) sm_o[wave][g][lane * 8 + e] = o[g][e];
       if (lane == 0) {
@@ -361,9 +383,10 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
   }
   __syncthreads();
 
-  // merge the 4 waves: wave 0, lane = dim
+  // merge the 4 waves: thread = dim (wave 0; at head dim 128 waves 0 and 1)
   const int H = p.H;
-  if (wave == 0) {
+  if (D == kWave ? wave == 0 : wave < D / kWave) {
+    const int dim = D == kWave ? lane : tid;
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       float mx = -INFINITY;
@@ -375,23 +398,24 @@ __global__ __launch_bounds__(NT) void decode_kernel(Params p) {
         for (int w = 0; w < NW; ++w) {
           const float sc = exp2f(sm_m[w][g] - mx);
           L += sm_l[w][g] * sc;
-          O += sm_o[w][g][lane] * sc;
+          O += sm_o[w][g][dim] * sc;
         }
       }
       const int h = kvh * G + g;
       if (p.nchunks == 1) {
-        p.out[(int64_t)b * H * D + h * D + lane] = f32_to_bf16(O / L);
+        p.out[(int64_t)b * H * D + h * D + dim] = f32_to_bf16(O / L);
       } else {
         const int64_t r = ((int64_t)b * H + h) * p.nchunks + c;
-        p.part_o[r * D + lane] = L > 0.f ? O / L : 0.f;
-        if (lane == 0) p.part_l[r] = L > 0.f ? mx + __log2f(L) : -INFINITY;
+        p.part_o[r * D + dim] = L > 0.f ? O / L : 0.f;
+        if (dim == 0) p.part_l[r] = L > 0.f ? mx + __log2f(L) : -INFINITY;
       }
     }
   }
 }
 
-// merge the chunk partials of one (b, head) row: one wave, lane = dim
-__global__ __launch_bounds__(kWave) void merge_kernel(Params p) {
+// merge the chunk partials of one (b, head) row: D threads (one wave, or two at 128), thread = dim
+template <int D>
+__global__ __launch_bounds__(D) void merge_kernel(Params p) {
   const int r = blockIdx.x, lane = threadIdx.x;  // r = b·H + h
   const int64_t r0 = (int64_t)r * p.nchunks;
   float mx = -INFINITY;
@@ -439,38 +463,45 @@ static at::Tensor decode_run(const at::Tensor& qkv, const at::Tensor& k_cache, c
   const char* op = sh ? "decode_attn_shared" : "decode_attn";
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1 &&
                   qkv.stride(0) % 8 == 0 && ((uintptr_t)qkv.data_ptr() & 15) == 0,
-              op, ": qkv must be a bf16 [B, (H + 2·Hkv)·64] GPU view, unit last stride, 16-B aligned rows");
+              op, ": qkv must be a bf16 [B, (H + 2·Hkv)·D] GPU view, unit last stride, 16-B aligned rows");
   const bool f8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  // the head dim is the caches' last dim: k, v, and with a prefix those too, all alike
+  TORCH_CHECK(k_cache.dim() == 4, op, ": caches must be [B, Hkv, Tmax, D], got ", k_cache.dim(), " dims");
+  const int64_t D = k_cache.size(3);
+  TORCH_CHECK(D == 64 || D == 128, op, ": head dim (the caches' last dim) must be 64 or 128, got ", D);
   auto check_caches = [&](const at::Tensor& k, const at::Tensor& v) {
     if (f8) {
       TORCH_CHECK(k.is_cuda() && k.is_contiguous() && k.dim() == 4 && k.size(3) == D && v.sizes() == k.sizes() &&
                       k.scalar_type() == at::kFloat8_e4m3fn && v.scalar_type() == at::kFloat8_e4m3fn &&
                       v.is_contiguous() && ((uintptr_t)k.data_ptr() & 7) == 0 && ((uintptr_t)v.data_ptr() & 7) == 0,
-                  op, ": fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, 64], 8-B aligned rows");
+                  op, ": fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, ", D, "], 8-B aligned rows");
     } else {
       TORCH_CHECK(k.is_cuda() && k.scalar_type() == at::kBFloat16 && k.is_contiguous() && k.dim() == 4 &&
                       k.size(3) == D && v.sizes() == k.sizes() && v.scalar_type() == at::kBFloat16 &&
                       v.is_contiguous() && ((uintptr_t)k.data_ptr() & 15) == 0 && ((uintptr_t)v.data_ptr() & 15) == 0,
-                  op, ": caches must be contiguous bf16 [B, Hkv, Tmax, 64]");
+                  op, ": caches must be contiguous bf16 [B, Hkv, Tmax, ", D, "]");
     }
   };
   check_caches(k_cache, v_cache);
   const int64_t B = qkv.size(0), Hkv = k_cache.size(1), Tmax = k_cache.size(2), H = n_head;
   TORCH_CHECK(k_cache.size(0) == B, op, ": cache batch ", k_cache.size(0), " != ", B);
   TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0 && H / Hkv <= 8, op, ": need H % Hkv == 0 and H / Hkv <= 8");
-  TORCH_CHECK(qkv.size(1) == (H + 2 * Hkv) * D, op, ": qkv width ", qkv.size(1), " != (H + 2·Hkv)·64");
+  TORCH_CHECK(qkv.size(1) == (H + 2 * Hkv) * D, op, ": qkv width ", qkv.size(1), " != (H + 2·Hkv)·", D,
+              " (H ", H, ", Hkv ", Hkv, ")");
   TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.is_contiguous() && pos.numel() == B,
               op, ": pos must be a contiguous int64 [B] GPU tensor");
   int64_t Tp = 0;  // logical keys: Tp prefix rows (decode_attn: none), then the Tmax rows of k_cache
   if (sh) {
     TORCH_CHECK(sh->k_prefix.scalar_type() == k_cache.scalar_type() && sh->v_prefix.scalar_type() == k_cache.scalar_type(),
                 op, ": prefix and own caches must have the same dtype (bf16 or float8_e4m3fn)");
+    TORCH_CHECK(sh->k_prefix.dim() == 4 && sh->k_prefix.size(3) == D, op, ": prefix caches of head dim ",
+                sh->k_prefix.dim() == 4 ? sh->k_prefix.size(3) : -1, " with own caches of head dim ", D);
     check_caches(sh->k_prefix, sh->v_prefix);
     Tp = sh->k_prefix.size(2);
     TORCH_CHECK(Tmax >= 1, op, ": the own caches need at least one row");
     TORCH_CHECK(sh->group >= 1 && B % sh->group == 0 && sh->k_prefix.size(0) == B / sh->group &&
                     sh->k_prefix.size(1) == Hkv,
-                op, ": prefix caches must be [B / group, Hkv, Tp, 64] for qkv [B, ...] (B ", B, ", group ", sh->group,
+                op, ": prefix caches must be [B / group, Hkv, Tp, ", D, "] for qkv [B, ...] (B ", B, ", group ", sh->group,
                 ", prefix batch ", sh->k_prefix.size(0), ")");
     TORCH_CHECK(sh->plen.is_cuda() && sh->plen.scalar_type() == at::kLong && sh->plen.is_contiguous() &&
                     sh->plen.numel() == B / sh->group,
@@ -491,13 +522,13 @@ static at::Tensor decode_run(const at::Tensor& qkv, const at::Tensor& k_cache, c
                     rope_cos->dim() == 2 && rope_cos->size(1) == D / 2 && rope_cos->size(0) >= Tp + Tmax &&
                     rope_sin->sizes() == rope_cos->sizes() && rope_sin->is_contiguous() &&
                     rope_sin->scalar_type() == at::kFloat,
-                op, sh ? ": rope tables must be contiguous float32 [>= Tp + Ts, 32]"
-                       : ": rope tables must be contiguous float32 [>= Tmax, 32]");
+                op, ": rope tables must be contiguous float32 [>= ", sh ? "Tp + Ts" : "Tmax", ", ", D / 2,
+                "] at head dim ", D);
   int nchunks, chunk;
   plan(B * Hkv, kv_len_max, nchunks, chunk);
   TORCH_CHECK(partials.is_cuda() && partials.scalar_type() == at::kFloat && partials.is_contiguous() &&
                   partials.numel() >= B * H * nchunks * (D + 1),
-              op, ": partials too small: need ", B * H * nchunks * (D + 1), " floats");
+              op, ": partials too small: need ", B * H * nchunks * (D + 1), " floats at head dim ", D);
   TORCH_CHECK(B * Hkv * nchunks < (1LL << 31) && Tmax * D * B * Hkv < (1LL << 62) && Tp * D * B * Hkv < (1LL << 62),
               op, ": grid too large");
   at::Tensor out = at::empty({B, H * D}, qkv.options().memory_format(at::MemoryFormat::Contiguous));
@@ -526,15 +557,21 @@ static at::Tensor decode_run(const at::Tensor& qkv, const at::Tensor& k_cache, c
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
   hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   const dim3 grid((unsigned)(B * Hkv * nchunks));
+  const bool wide = D == 128;
   switch (H / Hkv) {
-#define NBD_DECODE_GFS(g, f, s) hipLaunchKernelGGL((decode_kernel<g, f, s>), grid, dim3(NT), 0, st, p)
+#define NBD_DECODE_GFS(g, f, s)                                                         \
+  if (wide)                                                                             \
+    hipLaunchKernelGGL((decode_kernel<128, g, f, s>), grid, dim3(NT), 0, st, p);        \
+  else                                                                                  \
+    hipLaunchKernelGGL((decode_kernel<64, g, f, s>), grid, dim3(NT), 0, st, p)
 #define NBD_DECODE_G(g)                    \
   case g:                                  \
     if (sh) {                              \
-      if (f8)                              \
+      if (f8) {                            \
         NBD_DECODE_GFS(g, true, true);     \
-      else                                 \
+      } else {                             \
         NBD_DECODE_GFS(g, false, true);    \
+      }                                    \
     } else if (f8) {                       \
       NBD_DECODE_GFS(g, true, false);      \
     } else {                               \
@@ -554,7 +591,10 @@ static at::Tensor decode_run(const at::Tensor& qkv, const at::Tensor& k_cache, c
   }
   C10_HIP_KERNEL_LAUNCH_CHECK();
   if (nchunks > 1) {
-    hipLaunchKernelGGL(merge_kernel, dim3((unsigned)(B * H)), dim3(kWave), 0, st, p);
+    if (wide)
+      hipLaunchKernelGGL(merge_kernel<128>, dim3((unsigned)(B * H)), dim3(128), 0, st, p);
+    else
+      hipLaunchKernelGGL(merge_kernel<64>, dim3((unsigned)(B * H)), dim3(64), 0, st, p);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   return out;
@@ -567,8 +607,8 @@ at::Tensor decode_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
   return decode_run(qkv, k_cache, v_cache, pos, n_head, scale, kv_len_max, rope_cos, rope_sin, partials, nullptr);
 }
 
-// sequence s of qkv [S = B·group, ...] reads k_prefix / v_prefix [B, Hkv, Tp, 64] rows [0, plen[s / group]) and
-// its own rows k_own / v_own [S, Hkv, Ts, 64]; pos [S] are absolute positions, kv_len_max <= Tp + Ts
+// sequence s of qkv [S = B·group, ...] reads k_prefix / v_prefix [B, Hkv, Tp, D] rows [0, plen[s / group]) and
+// its own rows k_own / v_own [S, Hkv, Ts, D]; pos [S] are absolute positions, kv_len_max <= Tp + Ts
 at::Tensor decode_attn_shared_hip(const at::Tensor& qkv, const at::Tensor& k_prefix, const at::Tensor& v_prefix,
                                   const at::Tensor& plen, const at::Tensor& k_own, const at::Tensor& v_own,
                                   const at::Tensor& pos, int64_t group, int64_t n_head, double scale,

@@ -5,11 +5,11 @@ The reference's notebooks train; after training, a user of an interactive notebo
 
 * **prefill** — one pass over the (right-padded) prompts through the model's training kernels
   (HIP flash attention, fused GEMMs), storing each layer's k (rotated) and v into a
-  ``KVCache`` laid out [layer, batch, kv-head, position, 64] so a decode step streams one
+  ``KVCache`` laid out [layer, batch, kv-head, position, head dim] so a decode step streams one
   contiguous run of rows per head;
 * **decode** — one token per sequence per step: GEMMs on hipBLASLt (M = batch rows), and one HIP
   kernel per layer for RoPE + cache append + split-key attention with its merge
-  (``ops.decode_attention``, ``csrc/kernels/decode.hip``);
+  (``ops.decode_attention``, ``csrc/kernels/decode.hip``: head dim 64 or 128, bf16 or fp8 cache);
 * the positions live on the device, so the whole decode step — sampling included (Gumbel-max on
   the device RNG) — is captured once into a HIP graph and replayed per token: no host launch
   cost and no host sync per token (sequences that reach ``eos_token_id`` keep emitting it; the
@@ -47,7 +47,10 @@ def _kv_dtype(kv_dtype):
 
 
 class KVCache:
-    """k / v caches [n_layer, B, Hkv, t_max, D] plus the decode kernel's workspace.
+    """k / v caches [n_layer, B, Hkv, t_max, D] plus the decode kernel's workspace (D + 1 floats per
+    sequence, head and key chunk).  ``attend`` runs the HIP decode kernel at D = 64 and 128;
+    ``extend`` (continue) and the prefill attention have their kernels at 64 only and run the
+    PyTorch math at 128.
 
     ``dtype=torch.float8_e4m3fn``: rows are stored as ``ops.decode.q8`` makes them (clamped to
     ±448, round to nearest even, no scales) by ``store`` and by ``attend`` alike: half the bytes
@@ -62,7 +65,7 @@ class KVCache:
         self.v = torch.zeros(shape, dtype=dtype, device=device)
         from .ops.decode import partials_numel
 
-        self.workspace = torch.empty(partials_numel(batch, n_head, t_max), dtype=torch.float32, device=device)
+        self.workspace = torch.empty(partials_numel(batch, n_head, t_max, head_dim), dtype=torch.float32, device=device)
         self.kv_len_max: Optional[int] = None  # host bound on max(pos) + 1 (None = t_max)
         # set by every ``generate`` call (None on a fresh cache), both int64 [B] on the device:
         self.lengths: Optional[torch.Tensor] = None  # valid rows per sequence
@@ -147,7 +150,8 @@ class SharedPrefixKVCache:
         self.plen = torch.zeros(prompts, dtype=torch.int64, device=device)  # valid prefix rows per prompt
         from .ops.decode import partials_numel
 
-        self.workspace = torch.empty(partials_numel(self.batch, n_head, self.t_max), dtype=torch.float32, device=device)
+        self.workspace = torch.empty(partials_numel(self.batch, n_head, self.t_max, head_dim), dtype=torch.float32,
+                                     device=device)
         self.kv_len_max: Optional[int] = None  # host bound on max(pos) + 1 (None = t_max)
         self.lengths: Optional[torch.Tensor] = None  # int64 [prompts·group]: valid positions per sequence
         self.pending: Optional[torch.Tensor] = None  # the last emitted token of each, not yet in the cache

@@ -14,7 +14,11 @@ i.e. ~12 kernels per block instead of ~70, nothing that synchronises with the ho
 caching-allocator memory — so the whole training step captures into a HIP graph
 (``nbdistributed_amd.graphs.GraphedStep``).  The GPU path needs bf16/f16, head_dim 64 and a
 sequence length that is a multiple of 128; anything else (CPU, fp32) runs the same math in
-plain PyTorch.
+plain PyTorch.  Head dim 128 (Llama 3.x 3B / 8B, Mistral-7B, Qwen2.5): of the generation kernels
+the per-token one takes it — ``decode_step`` runs ``csrc/kernels/decode.hip`` at head dim 64 and
+128, bf16 and fp8 caches, shared prefix included — while the prefill (flash attention) and
+``extend`` (continue, ``csrc/kernels/append.hip``) have their kernels at 64 only and run the
+PyTorch math at 128.
 
 HF semantics kept by the one-line swap (``native()``):
 

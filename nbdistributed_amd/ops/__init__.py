@@ -26,9 +26,10 @@ gemm_linear /          bf16 GEMM on MFMA 16x16x32: x·Wᵀ, dy·W, dyᵀ·x     
 mlp_gelu /             + bias / GELU / GELU' / SwiGLU / SwiGLU'          swizzles, tr-reads)
 mlp_swiglu (K12)       epilogues, split-K, K-groups
 decode_attention (K13) one-token attention over a KV cache: RoPE +      decode.hip (split keys,
-                       cache append + softmax·V + chunk merge           merge kernel)
+                       cache append + softmax·V + chunk merge; head     merge kernel)
+                       dim 64 or 128
 decode_attention_      the same over a prompt's shared prefix rows plus  decode.hip (decode_kernel
-shared (K13)           the sample's own rows (several samples / prompt)  <G, F8, SHARED>)
+shared (K13)           the sample's own rows (several samples / prompt)  <D, G, F8, SHARED>)
 linear_small (K14)     decode linear: LN/RMS prologue + x·Wᵀ (MFMA) +   smallm.hip
                        bias / GELU / SwiGLU / residual epilogue, M ≤ 64
 packed_bounds (K16)    position_ids of packed rows -> per-query start /  packed.hip (one wave per

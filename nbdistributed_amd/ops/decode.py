@@ -1,13 +1,14 @@
 """Decode attention over a KV cache (K13): one new token per sequence, cache append fused.
 
-``csrc/kernels/decode.hip`` on GPU (bf16, head dim 64, up to 8 query heads per key/value head);
+``csrc/kernels/decode.hip`` on GPU (bf16, head dim 64 or 128, up to 8 query heads per key/value head);
 the same math in PyTorch otherwise (CPU, fp32) — also the numerics reference of the GPU tests.
 The caches are bf16 or, with no scales, ``float8_e4m3fn`` (:func:`q8`: half the bytes a decode
 step streams); qkv and the output stay bf16.
 Shared prefix (``decode_attention_shared``): ``group`` consecutive sequences read one prompt's prefix
 rows and then their own — several samples per prompt with the prompt held once.
 Block append (K17, ``csrc/kernels/append.hip``): several new tokens per sequence at per-sequence
-offsets — what continuing from a returned cache runs instead of a second prefill.
+offsets — what continuing from a returned cache runs instead of a second prefill (head dim 64
+only: at 128 it runs the PyTorch version).
 """
 from __future__ import annotations
 
@@ -16,10 +17,14 @@ from typing import Optional
 from ._lib import _require
 
 
-def partials_numel(batch: int, n_head: int, t_max: int) -> int:
-    """fp32 workspace the kernel needs for its chunk partials (worst case over key bounds ≤ ``t_max``)."""
+DECODE_HEAD_DIMS = (64, 128)  # the head dims decode.hip is instantiated for
+
+
+def partials_numel(batch: int, n_head: int, t_max: int, head_dim: int = 64) -> int:
+    """fp32 workspace the kernel needs for its chunk partials (worst case over key bounds ≤ ``t_max``):
+    ``head_dim`` + 1 floats — the chunk's output row and its log-sum-exp — per (sequence, head, chunk)."""
     nchunks = min(64, max(1, -(-t_max // 128)))
-    return batch * n_head * nchunks * 65
+    return batch * n_head * nchunks * (head_dim + 1)
 
 
 FP8_MAX = 448.0  # the largest finite float8_e4m3fn (OCP e4m3: no inf)
@@ -45,7 +50,7 @@ def decode_supported(qkv, k_cache, n_head: int) -> bool:
 
     Hkv = k_cache.shape[1]
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_cache.dtype in (torch.bfloat16, torch.float8_e4m3fn)
-            and k_cache.shape[-1] == 64 and n_head % Hkv == 0 and n_head // Hkv <= 8)
+            and k_cache.shape[-1] in DECODE_HEAD_DIMS and n_head % Hkv == 0 and n_head // Hkv <= 8)
 
 
 def _rope_at(x, cos, sin, pos):
@@ -101,7 +106,8 @@ def decode_attention(qkv, k_cache, v_cache, pos, n_head: int, scale: Optional[fl
     (cos, sin) tables) and v are written into the caches at ``pos[b]`` and the token attends to
     rows 0..pos[b].  ``kv_len_max`` bounds max(pos) + 1 (default Tmax; smaller = fewer idle
     workgroups); ``workspace`` = fp32 chunk partials [≥ :func:`partials_numel`] (held by
-    ``generation.KVCache``; allocated per call if None).  Returns [B, H·D]."""
+    ``generation.KVCache``; allocated per call if None).  Returns [B, H·D].  The HIP kernel takes
+    D = 64 and 128; any other head dim runs :func:`decode_attention_reference`."""
     import torch
 
     D = k_cache.shape[-1]
@@ -110,7 +116,7 @@ def decode_attention(qkv, k_cache, v_cache, pos, n_head: int, scale: Optional[fl
         _require()
         B, Tmax = k_cache.shape[0], k_cache.shape[2]
         if workspace is None:
-            workspace = torch.empty(partials_numel(B, n_head, Tmax), dtype=torch.float32, device=qkv.device)
+            workspace = torch.empty(partials_numel(B, n_head, Tmax, D), dtype=torch.float32, device=qkv.device)
         cos, sin = rope if rope is not None else (None, None)
         if qkv.stride(-1) != 1 or qkv.stride(0) % 8 or qkv.data_ptr() % 16:
             qkv = qkv.contiguous()
@@ -125,7 +131,8 @@ def decode_shared_supported(qkv, k_prefix, k_own, n_head: int) -> bool:
 
     Hkv = k_own.shape[1]
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_own.dtype in (torch.bfloat16, torch.float8_e4m3fn)
-            and k_prefix.dtype == k_own.dtype and k_own.shape[-1] == 64 and k_prefix.shape[-1] == 64
+            and k_prefix.dtype == k_own.dtype and k_own.shape[-1] in DECODE_HEAD_DIMS
+            and k_prefix.shape[-1] == k_own.shape[-1]
             and n_head % Hkv == 0 and n_head // Hkv <= 8)
 
 
@@ -197,7 +204,8 @@ def decode_attention_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, gr
     own row ``pos - plen`` and the token attends logical keys 0..pos.  ``plen`` is clamped to
     [0, Tp] and ``pos`` to [plen, plen + Ts - 1] first.  ``kv_len_max`` bounds max(pos) + 1 (default
     Tp + Ts); ``workspace`` as in :func:`decode_attention`, sized for S sequences and Tp + Ts keys.
-    bf16 or ``float8_e4m3fn`` caches (prefix and own alike).  Returns [S, H·D]."""
+    bf16 or ``float8_e4m3fn`` caches (prefix and own alike), D = 64 or 128 on the HIP kernel (prefix and
+    own alike).  Returns [S, H·D]."""
     import torch
 
     D = k_own.shape[-1]
@@ -209,7 +217,7 @@ def decode_attention_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, gr
         _require()
         S, T = k_own.shape[0], k_prefix.shape[2] + k_own.shape[2]
         if workspace is None:
-            workspace = torch.empty(partials_numel(S, n_head, T), dtype=torch.float32, device=qkv.device)
+            workspace = torch.empty(partials_numel(S, n_head, T, D), dtype=torch.float32, device=qkv.device)
         cos, sin = rope if rope is not None else (None, None)
         if qkv.stride(-1) != 1 or qkv.stride(0) % 8 or qkv.data_ptr() % 16:
             qkv = qkv.contiguous()
