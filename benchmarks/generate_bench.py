@@ -39,6 +39,14 @@ against 2h at 64).  Both arms in one process, rounds interleaved.
 
     python benchmarks/generate_bench.py --head-dim 128 [--layers 4] [--batches 1,8,32]
         [--hist 128,4096] [--rounds 7] [--out table.json]
+
+``--continue --head-dim 128``: the time to the first token of turn 2 on that stack — continuing
+with the block-append kernel at head dim 128 against the same call with
+``ops.decode.append_supported`` patched to False (the PyTorch path) and against the re-prefill of
+history + turn — and ``ops.append_attention`` alone against head dim 64 at equal streamed bytes.
+
+    python benchmarks/generate_bench.py --continue --head-dim 128 [--layers 4] [--batches 1,8]
+        [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -454,10 +462,125 @@ def head_dim_bench(a):
             json.dump(res, f, indent=1)
 
 
+def head_dim_continue_bench(a):
+    """``--continue --head-dim 128``: the time to the first token of turn 2 on the Llama-3.2-3B-shaped
+    stack of ``head_dim_bench``, three arms in one process with their rounds interleaved —
+    (a) ``generate(turn, 1, cache=cache)`` with the block-append kernel, (b) the same call with
+    ``ops.decode.append_supported`` patched to False (the PyTorch path head dim 128 ran before),
+    (c) ``generate(history + turn, 1)``, the re-prefill — and ``ops.append_attention`` alone (both
+    launches) at 128 against 64 at equal streamed bytes (Hkv = h at 128, 2h at 64; same B, G, Tn, start)."""
+    import contextlib
+    import statistics
+    from unittest import mock
+
+    from nbdistributed_amd import ops
+    from nbdistributed_amd.generation import generate
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+
+    D = a.head_dim
+    med = lambda xs: round(statistics.median(xs), 3)  # noqa: E731
+    span = lambda xs: [round(min(xs), 3), round(max(xs), 3)]  # noqa: E731
+    hists = [int(x) for x in a.hist.split(",")]
+    turns = [int(x) for x in a.turn.split(",")]
+    batches = [int(x) for x in a.batches.split(",")]
+    res = {"what": f"ms to the first token of turn 2 at head dim {D}: Llama-3.2-3B-shaped stack of {a.layers} layers (hidden "
+                   f"3072, 24 / 8 heads), random bf16 weights, eager; (a) continue with the block-append kernel, (b) the "
+                   f"same call with append_supported patched to False, (c) re-prefill of history + turn; and "
+                   f"ops.append_attention alone at {D} vs 64 at equal streamed bytes; rounds interleaved",
+           "layers": a.layers, "rounds": a.rounds, "points": [], "kernel": []}
+    torch.manual_seed(0)
+    vocab = 32000
+    cfg = LlamaConfig(vocab_size=vocab, hidden_size=3072, intermediate_size=8192, num_hidden_layers=a.layers,
+                      num_attention_heads=24, num_key_value_heads=8, max_position_embeddings=8192, explicit_head_dim=D)
+    m = LlamaForCausalLM(cfg).to("cuda", torch.bfloat16).eval()
+    off = lambda: mock.patch.object(ops.decode, "append_supported", lambda *x: False)  # noqa: E731
+    for B in batches:
+        for hist in hists:
+            # turn 1 leaves hist - 1 rows in the cache and one pending token: a history of hist tokens
+            ids = torch.randint(1, vocab, (B, hist - 8), device="cuda")
+            out1, cache = generate(m, ids, 8, t_max=-(-(hist + max(turns) + 2) // 128) * 128, graph=False, return_cache=True)
+            len0, pend0 = cache.lengths.clone(), cache.pending.clone()
+            assert ops.append_supported(torch.zeros(1, 1, 1, dtype=torch.bfloat16, device="cuda"), cache.k[0], 24)
+            for turn in turns:
+                new = torch.randint(1, vocab, (B, turn), device="cuda")
+                whole = torch.cat([out1, new], 1)
+
+                def cont(patched=False):
+                    cache.lengths, cache.pending = len0.clone(), pend0.clone()
+                    with off() if patched else contextlib.nullcontext():
+                        return generate(m, new, 1, cache=cache, graph=False)
+
+                arms = (("kernel", cont), ("fallback", lambda: cont(True)),
+                        ("reprefill", lambda: generate(m, whole, 1, graph=False)))
+                first = {name: fn()[:, -1] for name, fn in arms}  # (also the warm-up of every arm)
+                ms = {name: [] for name, _ in arms}
+                for _ in range(a.rounds):  # interleaved: drift hits the arms alike
+                    for name, fn in arms:
+                        torch.cuda.synchronize()
+                        t = time.perf_counter()
+                        fn()
+                        torch.cuda.synchronize()
+                        ms[name].append((time.perf_counter() - t) * 1e3)
+                row = dict(batch=B, history=hist, turn=turn)
+                for name, _ in arms:
+                    row[name + "_ms"], row[name + "_min_max"] = med(ms[name]), span(ms[name])
+                for name in ("fallback", "reprefill"):
+                    r = [x / y for x, y in zip(ms[name], ms["kernel"])]  # per round: the arms ran back to back
+                    row[name + "_over_kernel"], row[name + "_over_kernel_min_max"] = med(r), span(r)
+                row["first_token_same_as_fallback"] = bool((first["kernel"] == first["fallback"]).all())
+                row["first_token_same_as_reprefill"] = bool((first["kernel"] == first["reprefill"]).all())
+                print(json.dumps(row), flush=True)
+                res["points"].append(row)
+            del cache
+            torch.cuda.empty_cache()
+    del m
+    torch.cuda.empty_cache()
+    G, h = 3, 8
+    for B in batches:
+        for hist in hists:
+            for turn in turns:
+                Tn, Tmax = turn + 1, -(-(hist + max(turns) + 2) // 128) * 128
+                fns = {}
+                for d, hk in ((D, h), (64, 2 * h)):
+                    H = G * hk
+                    kc = torch.randn(B, hk, Tmax, d, device="cuda").to(torch.bfloat16)
+                    vc = torch.randn(B, hk, Tmax, d, device="cuda").to(torch.bfloat16)
+                    qkv = torch.randn(B, Tn, (H + 2 * hk) * d, device="cuda").to(torch.bfloat16)
+                    st = torch.full((B,), hist - 1, device="cuda", dtype=torch.int64)
+                    nn = torch.full((B,), Tn, device="cuda", dtype=torch.int64)
+                    rope = ops.rope_tables(Tmax, d, 10000.0, "cuda")
+                    fns[d] = (lambda qkv=qkv, kc=kc, vc=vc, st=st, nn=nn, H=H, rope=rope:
+                              ops.append_attention(qkv, kc, vc, st, nn, H, rope=rope, kv_len_max=hist + Tn))
+                    for _ in range(3):
+                        fns[d]()
+                torch.cuda.synchronize()
+                us = {d: [] for d in fns}
+                n = 20
+                for _ in range(a.rounds):
+                    for d, f in fns.items():
+                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        s.record()
+                        for _ in range(n):
+                            f()
+                        e.record()
+                        e.synchronize()
+                        us[d].append(s.elapsed_time(e) / n * 1e3)
+                ratios = [x / y for x, y in zip(us[D], us[64])]
+                row = dict(B=B, G=G, history=hist, Tn=Tn, Hkv_128=h, Hkv_64=2 * h, cache_bytes_read=2 * B * h * (hist + Tn - 1) * D * 2,
+                           us_128=round(statistics.median(us[D]), 2), us_64=round(statistics.median(us[64]), 2),
+                           ratio_128_over_64=round(statistics.median(ratios), 3), ratio_min_max=span(ratios))
+                print(json.dumps(row), flush=True)
+                res["kernel"].append(row)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--head-dim", dest="head_dim", type=int, default=0, choices=[0, 128],
-                    help="the head-dim-128 decode arm (see the module docstring): --layers, --batches, --hist, --rounds")
+                    help="the head-dim-128 decode arm, with --continue the head-dim-128 multi-turn arm (see the module "
+                         "docstring): --layers, --batches, --hist, --rounds")
     ap.add_argument("--layers", type=int, default=4, help="--head-dim: layers of the Llama-3.2-3B-shaped stack")
     ap.add_argument("--shared", type=int, default=0, metavar="R",
                     help="R samples per prompt over one shared prompt cache vs repeated prompts: --models, --batches "
@@ -483,6 +606,10 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.head_dim and a.cont:
+        if a.batches == "1,8,32":
+            a.batches = "1,8"
+        return head_dim_continue_bench(a)
     if a.head_dim:
         if a.hist == "512,2048,4096":
             a.hist = "128,4096"

@@ -169,5 +169,49 @@ struct Stage2 {
   }
 };
 
+// ---------------------------------------------------------------------------------------------
+// head-dim-generic forms, used by append.hip only (D = 64 | 128).  At D = 64 each expands to the
+// fixed-width helper above it is named after; attn.hip keeps the fixed ones.
+
+// rope8 with the tables' row stride (= D/2, the distance to the rotation partner) as a parameter:
+// x holds dims [d0, d0+8), y their partners [d0 + HALF, d0 + HALF + 8); cos/sin = [T_max, HALF]
+template <int HALF>
+__device__ __forceinline__ void rope8_hd(s8v& x, s8v& y, const Rope& rp, int t, int d0) {
+  const float4* c4 = reinterpret_cast<const float4*>(rp.cos + (int64_t)t * HALF + d0);
+  const float4* s4 = reinterpret_cast<const float4*>(rp.sin + (int64_t)t * HALF + d0);
+  const float4 ca = c4[0], cb = c4[1], sa = s4[0], sb = s4[1];
+  const float c[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
+  const float sn[8] = {sa.x, sa.y, sa.z, sa.w, sb.x, sb.y, sb.z, sb.w};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float a = bf16_to_f32((uint16_t)x[j]), b = bf16_to_f32((uint16_t)y[j]);
+    x[j] = (short)bf(a * c[j] - b * sn[j]);
+    y[j] = (short)bf(b * c[j] + a * sn[j]);
+  }
+}
+
+// rope_frag over D/16 fragments (element s covers dims 16s + 8h + [0, 8)): the partner of
+// fragment s is fragment s + D/32 — (f[0], f[2]), (f[1], f[3]) at 64; (f[s], f[s + 4]) at 128
+template <int D>
+__device__ __forceinline__ void rope_frag_hd(s8v (&f)[D / 16], const Rope& rp, int t, int h) {
+#pragma unroll
+  for (int s = 0; s < D / 32; ++s) rope8_hd<D / 2>(f[s], f[s + D / 32], rp, t, 16 * s + 8 * h);
+}
+
+// Stage2 for 64 rows x D dims: 8·D 16-B chunks, D/32 per thread, D/8 consecutive threads per row
+// (a wave's load covers whole rows; 8 consecutive lanes of a ds_write_b128 cover 128 contiguous
+// bytes = all 32 banks once)
+template <int D>
+struct StageRows {
+  s8v a[D / 32];
+  __device__ __forceinline__ void store(uint16_t* lds, int stride, int tid) const {
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+      const int c = tid + i * NT;
+      st16(lds + (c >> (D == 64 ? 3 : 4)) * stride + (c & (D / 8 - 1)) * 8, a[i]);
+    }
+  }
+};
+
 }  // namespace attn
 }  // namespace nbd

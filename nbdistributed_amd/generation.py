@@ -48,9 +48,8 @@ def _kv_dtype(kv_dtype):
 
 class KVCache:
     """k / v caches [n_layer, B, Hkv, t_max, D] plus the decode kernel's workspace (D + 1 floats per
-    sequence, head and key chunk).  ``attend`` runs the HIP decode kernel at D = 64 and 128;
-    ``extend`` (continue) and the prefill attention have their kernels at 64 only and run the
-    PyTorch math at 128.
+    sequence, head and key chunk).  ``attend`` (decode) and ``extend`` (continue) run their HIP kernels at D = 64
+    and 128; the prefill attention has its kernel at 64 only and runs the PyTorch math at 128.
 
     ``dtype=torch.float8_e4m3fn``: rows are stored as ``ops.decode.q8`` makes them (clamped to
     ±448, round to nearest even, no scales) by ``store`` and by ``attend`` alike: half the bytes

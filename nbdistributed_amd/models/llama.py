@@ -15,10 +15,10 @@ caching-allocator memory — so the whole training step captures into a HIP grap
 (``nbdistributed_amd.graphs.GraphedStep``).  The GPU path needs bf16/f16, head_dim 64 and a
 sequence length that is a multiple of 128; anything else (CPU, fp32) runs the same math in
 plain PyTorch.  Head dim 128 (Llama 3.x 3B / 8B, Mistral-7B, Qwen2.5): of the generation kernels
-the per-token one takes it — ``decode_step`` runs ``csrc/kernels/decode.hip`` at head dim 64 and
-128, bf16 and fp8 caches, shared prefix included — while the prefill (flash attention) and
-``extend`` (continue, ``csrc/kernels/append.hip``) have their kernels at 64 only and run the
-PyTorch math at 128.
+the per-token one and the block append take it — ``decode_step`` runs ``csrc/kernels/decode.hip``
+at head dim 64 and 128, bf16 and fp8 caches, shared prefix included, and ``extend`` (continue)
+runs ``csrc/kernels/append.hip`` at 64 and 128 on a bf16 cache — while the prefill (flash
+attention) has its kernel at 64 only and runs the PyTorch math at 128.
 
 HF semantics kept by the one-line swap (``native()``):
 

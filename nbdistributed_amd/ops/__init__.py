@@ -38,7 +38,7 @@ packed_bounds (K16)    position_ids of packed rows -> per-query start /  packed.
 append_attention (K17) a block of new tokens over a KV cache (multi-turn  append.hip (append_kv +
                        continuation): RoPE + cache append at per-       fwd_kernel's body over the
                        sequence offsets + causal attention over the      cache; attn_common.h)
-                       cache; device-side start / nnew
+                       cache; device-side start / nnew; head dim 64 | 128
 =====================  ==============================================  =========================
 
 GPU tensors always go to the HIP kernels; if ``libnbd_ops.so`` cannot be loaded on a GPU box the

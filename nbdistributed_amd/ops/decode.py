@@ -7,8 +7,8 @@ step streams); qkv and the output stay bf16.
 Shared prefix (``decode_attention_shared``): ``group`` consecutive sequences read one prompt's prefix
 rows and then their own — several samples per prompt with the prompt held once.
 Block append (K17, ``csrc/kernels/append.hip``): several new tokens per sequence at per-sequence
-offsets — what continuing from a returned cache runs instead of a second prefill (head dim 64
-only: at 128 it runs the PyTorch version).
+offsets — what continuing from a returned cache runs instead of a second prefill (bf16 cache,
+head dim 64 or 128).
 """
 from __future__ import annotations
 
@@ -227,12 +227,15 @@ def decode_attention_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, gr
 
 
 # ------------------------------------------------------------------ block append (K17)
+APPEND_HEAD_DIMS = (64, 128)  # the head dims append.hip is instantiated for
+
+
 def append_supported(qkv, k_cache, n_head: int) -> bool:
     import torch
 
     Hkv = k_cache.shape[1]
     return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16
-            and k_cache.shape[-1] == 64 and n_head % Hkv == 0)
+            and k_cache.shape[-1] in APPEND_HEAD_DIMS and n_head % Hkv == 0)
 
 
 def _append_span(start, nnew, Tn: int, limit: int):
@@ -296,8 +299,10 @@ def append_attention(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Opt
     start[b] + i when ``rope`` = (cos, sin) tables) and v are written to cache row start[b] + i and
     query i attends rows 0..start[b] + i; no later row influences it, whatever it holds, and rows
     ≥ start[b] + nnew[b] are not written.  ``kv_len_max`` is a host bound on max(start + nnew)
-    (default Tmax).  Returns [B, Tn, H·D] with exact zeros on the padding rows.  GPU bf16, head dim
-    64 → ``csrc/kernels/append.hip``; elsewhere the same math in PyTorch."""
+    (default Tmax).  Returns [B, Tn, H·D] with exact zeros on the padding rows.  GPU bf16 (qkv and
+    caches), head dim 64 or 128 (the caches' last dim; ``rope`` tables [≥ Tmax, D/2]) →
+    ``csrc/kernels/append.hip``; elsewhere — CPU, other dtypes, other head dims — the same math in
+    PyTorch (:func:`append_attention_reference`)."""
     import torch
 
     D = k_cache.shape[-1]
