@@ -47,6 +47,13 @@ history + turn — and ``ops.append_attention`` alone against head dim 64 at equ
 
     python benchmarks/generate_bench.py --continue --head-dim 128 [--layers 4] [--batches 1,8]
         [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
+
+``--continue --split [--head-dim 128]``: the key split of the block-append kernel, ``auto`` (the kernel's
+plan) against ``0`` (the unsplit kernel), rounds interleaved: ``ops.append_attention`` alone and the time
+to the first token of turn 2 (SmolLM2-135M, or the head-dim-128 stack), same points.
+
+    python benchmarks/generate_bench.py --continue --split [--head-dim 128] [--layers 4] [--batches 1,8]
+        [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -576,6 +583,109 @@ def head_dim_continue_bench(a):
             json.dump(res, f, indent=1)
 
 
+def split_bench(a):
+    """``--continue --split`` (with ``--head-dim 128``: the Llama-3.2-3B-shaped stack, else SmolLM2-135M):
+    the key split of the block-append kernel, ``auto`` (the kernel's plan) against ``0`` (never: the
+    unsplit kernel), rounds interleaved in one process.  Per (batch, history, turn):
+    ``ops.append_attention`` alone (all its launches) and the time to the first token of turn 2.  A
+    point where ``auto`` is slower than ``0`` by more than ``0``'s own round-to-round spread is marked
+    ``auto_slower``: the plan's thresholds have to move until that point runs unsplit."""
+    import statistics
+    from unittest import mock
+
+    from nbdistributed_amd import ops
+    from nbdistributed_amd.generation import generate
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+
+    D = a.head_dim or 64
+    med = lambda xs: round(statistics.median(xs), 3)  # noqa: E731
+    span = lambda xs: [round(min(xs), 3), round(max(xs), 3)]  # noqa: E731
+    hists = [int(x) for x in a.hist.split(",")]
+    turns = [int(x) for x in a.turn.split(",")]
+    batches = [int(x) for x in a.batches.split(",")]
+    arms = (("auto", 0), ("off", 1))  # the op's key_splits
+
+    def row_of(t, **key):
+        row = dict(key)
+        for name, _ in arms:
+            row[name], row[name + "_min_max"] = med(t[name]), span(t[name])
+        spread = max(t["off"]) - min(t["off"])
+        row["off_over_auto"] = round(statistics.median([x / y for x, y in zip(t["off"], t["auto"])]), 3)
+        row["auto_slower"] = bool(statistics.median(t["auto"]) > statistics.median(t["off"]) + spread)
+        print(json.dumps(row), flush=True)
+        return row
+
+    res = {"what": f"key split of the block-append kernel at head dim {D}: auto (the plan) vs 0 (the unsplit kernel), rounds "
+                   f"interleaved; kernel = us per ops.append_attention call, points = ms to the first token of turn 2",
+           "rounds": a.rounds, "kernel": [], "points": []}
+    H, Hkv = (24, 8) if D == 128 else (9, 3)
+    n = 20
+    for B in batches:
+        for hist in hists:
+            for turn in turns:
+                Tn, Tmax = turn + 1, -(-(hist + max(turns) + 2) // 128) * 128
+                kc = torch.randn(B, Hkv, Tmax, D, device="cuda").to(torch.bfloat16)
+                vc = torch.randn(B, Hkv, Tmax, D, device="cuda").to(torch.bfloat16)
+                qkv = torch.randn(B, Tn, (H + 2 * Hkv) * D, device="cuda").to(torch.bfloat16)
+                st = torch.full((B,), hist - 1, device="cuda", dtype=torch.int64)
+                nn = torch.full((B,), Tn, device="cuda", dtype=torch.int64)
+                rope = ops.rope_tables(Tmax, D, 10000.0, "cuda")
+                f = lambda ks: ops.append_attention(qkv, kc, vc, st, nn, H, rope=rope, kv_len_max=hist + Tn, key_splits=ks)  # noqa: E731
+                for _, ks in arms:
+                    for _ in range(3):
+                        f(ks)
+                torch.cuda.synchronize()
+                us = {name: [] for name, _ in arms}
+                for _ in range(a.rounds):
+                    for name, ks in arms:
+                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        s.record()
+                        for _ in range(n):
+                            f(ks)
+                        e.record()
+                        e.synchronize()
+                        us[name].append(s.elapsed_time(e) / n * 1e3)
+                res["kernel"].append(row_of(us, B=B, H=H, Hkv=Hkv, history=hist, Tn=Tn,
+                                            key_splits=ops.append_key_splits(B, H, Tn, hist + Tn, D)))
+    torch.manual_seed(0)
+    if D == 128:
+        vocab = 32000
+        cfg = LlamaConfig(vocab_size=vocab, hidden_size=3072, intermediate_size=8192, num_hidden_layers=a.layers,
+                          num_attention_heads=24, num_key_value_heads=8, max_position_embeddings=8192, explicit_head_dim=D)
+        m = LlamaForCausalLM(cfg).to("cuda", torch.bfloat16).eval()
+    else:
+        m, vocab, _, _ = _bench_model("smollm2", max(hists) + max(turns) + 2)
+    for B in batches:
+        for hist in hists:
+            ids = torch.randint(1, vocab, (B, hist - 8), device="cuda")
+            _, cache = generate(m, ids, 8, t_max=-(-(hist + max(turns) + 2) // 128) * 128, graph=False, return_cache=True)
+            len0, pend0 = cache.lengths.clone(), cache.pending.clone()
+            for turn in turns:
+                new = torch.randint(1, vocab, (B, turn), device="cuda")
+
+                def cont(ks):
+                    cache.lengths, cache.pending = len0.clone(), pend0.clone()
+                    with mock.patch.object(ops.decode, "APPEND_KEY_SPLITS", ks):
+                        return generate(m, new, 1, cache=cache, graph=False)
+
+                first = {name: cont(ks)[:, -1] for name, ks in arms}  # (also the warm-up of both arms)
+                ms = {name: [] for name, _ in arms}
+                for _ in range(a.rounds):
+                    for name, ks in arms:
+                        torch.cuda.synchronize()
+                        t = time.perf_counter()
+                        cont(ks)
+                        torch.cuda.synchronize()
+                        ms[name].append((time.perf_counter() - t) * 1e3)
+                res["points"].append(row_of(ms, batch=B, history=hist, turn=turn,
+                                            first_token_same=bool((first["auto"] == first["off"]).all())))
+            del cache
+            torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--head-dim", dest="head_dim", type=int, default=0, choices=[0, 128],
@@ -591,6 +701,8 @@ def main():
                          "--batches, --prompt and the longest history each model allows, --new, --rounds")
     ap.add_argument("--max-positions", type=int, default=8192, help="--kv-dtype: cap on the longest history")
     ap.add_argument("--continue", dest="cont", action="store_true", help="the multi-turn arm (see the module docstring)")
+    ap.add_argument("--split", action="store_true",
+                    help="with --continue [--head-dim 128]: the block-append kernel's key split, auto vs never")
     ap.add_argument("--models", default="smollm2,gpt2")
     ap.add_argument("--hist", default="512,2048,4096")
     ap.add_argument("--turn", default="1,32,128")
@@ -606,6 +718,10 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.split and a.cont:
+        if a.batches == "1,8,32":
+            a.batches = "1,8"
+        return split_bench(a)
     if a.head_dim and a.cont:
         if a.batches == "1,8,32":
             a.batches = "1,8"

@@ -24,7 +24,7 @@
 //     visible key `lim`, a wave the first / last lane's (lim0 / lim31, wave-uniform).  Tiles past
 //     lim31 are skipped, compares run only in the 32x32 blocks that hold a key > lim0.
 //   * padding queries (i >= nnew[b]) take the last valid query's limit, so no lane ever sees an
-//     empty row (every sweep starts at tile 0 and key 0 <= every lim: the running maximum is
+//     empty row (every unsplit sweep starts at tile 0 and key 0 <= every lim: the running maximum is
 //     finite after the first tile, and exp2(-inf - (-inf)) is never reached with m = -inf as the
 //     start); their result is dropped and exact zeros are stored.  A wave or workgroup whose
 //     queries are all padding runs no MFMA but meets every barrier.
@@ -35,10 +35,41 @@
 //   * start / nnew are clamped before they address anything: 0 <= start <= L - 1 and
 //     0 <= nnew <= min(Tn, L - start) with L = min(Tmax, kv_len_max); row indices of staged
 //     tiles and of padding queries are clamped into their tensors on top of that.
-//   * no split over keys: the grid is B · H · ceil(Tn / 128) workgroups (heaviest query block
-//     first) and each sweeps its keys sequentially.  docs/FINDINGS.md has what that costs for
-//     batch 1 over a long history.
+//   * the unsplit grid is B · H · ceil(Tn / 128) workgroups (heaviest query block first), each
+//     sweeping its keys sequentially: append_attn_kernel<D, false>.
 // Tn needs no padding: the kernel clamps its query loads and bounds its stores at Tn.
+//
+// Key split (append_attn_kernel<D, true> + append_merge_kernel<D>; flash-decoding partials as in
+// decode.hip).  Few sequences over a long history leave the unsplit grid on a fraction of the
+// 256 CUs, and one workgroup's sweep is the time.  The host's plan() then cuts the sweep:
+//   * grid B · H · nqb · nsplit, (query block, chunk) slowest — the last query block first, its
+//     chunks from key 0 up (the low chunks are the ones every block has).  A workgroup owns
+//     (batch · head, query block, chunk c) and sweeps the 64-key tiles [c · chunk_tiles,
+//     (c + 1) · chunk_tiles) cut at the block's last tile; chunk edges are tile edges, the body
+//     is the unsplit one.  A chunk that starts past the block's last tile (short history, early
+//     query block) returns before it stages anything — uniform in the workgroup, no barrier met.
+//   * partials, fp32: per (batch · head, query block, chunk, wave) one tile O^T[D][32] of the
+//     chunk's normalised output followed by lse[32] = m + log2(l).  Dim-major with the 32
+//     queries contiguous is the accumulator as the wave holds it (dim in the register, query on
+//     the lane): every store instruction writes two whole 128-B lines, nothing is transposed,
+//     and the merge reads the lines back the same way.
+//   * empty rows: with c > 0 a lane, or a whole wave, of a live workgroup may see no key of its
+//     chunk (the diagonal start + i crosses the chunk edge inside the block).  Its registers
+//     hold nothing (or NaN, exp2(-inf + inf)); MFMA columns are per query, so nothing leaks into
+//     a neighbour.  Such a lane stores nothing, and the merge never reads its slot: it derives
+//     from start / nnew that query i has the chunks 0 .. (start + i) / (64 · chunk_tiles) and
+//     reads exactly those — each written by this call (the chunk's first tile held a visible
+//     key: m finite, l > 0).  No -inf markers, no workspace read that this call did not write.
+//   * append_merge_kernel: a second small launch (why not the last-arriving workgroup:
+//     decode.hip).  Per query: max of the lse values, then the exp2-weighted sum, chunks in index
+//     order — bit-reproducible.  It writes the bf16 row and the zeros of the padding rows.
+//   * both grids and the workspace size (at::empty inside the op, like `out`) follow host values
+//     only: B, H, Tn, kv_len_max, D.  The op still captures into a HIP graph.
+//   * the <D, false> instantiations are the kernels they were, instruction for instruction (one
+//     kernarg displacement aside: the grid size sits behind the new fields).  Compiler's report,
+//     VGPR / AGPR / scratch / waves per SIMD / LDS: <64, false> 171 / 0 / 0 / 2 / 21 504,
+//     <64, true> 171 / 0 / 0 / 2 / 21 504, <128, false> 256 / 131 / 0 / 1 / 37 888, <128, true>
+//     256 / 133 / 0 / 1 / 37 888; merge 52 (64) and 90 (128) VGPR, no LDS.
 //
 // Head dim: both kernels take it as a template parameter, D = 64 | 128 (the host reads it from the
 // caches' last dim); "64" above stands for D.  The algorithm is the same; what follows D:
@@ -93,6 +124,9 @@ struct AppendParams {
   Rope rp;
   int H, Hkv, Tn, Tmax, L, nqb;  // L = min(Tmax, kv_len_max): the clamp of start + nnew
   float sc2;                     // softmax scale · log2(e)
+  // the key split (append_attn_kernel<D, true> and append_merge_kernel; unread otherwise)
+  float* ws;                // chunk partials: [B·H, nqb, nsplit, 4 waves] tiles of (D + 1) x 32 fp32
+  int nsplit, chunk_tiles;  // chunk c of a query block = its 64-key tiles [c·chunk_tiles, (c + 1)·chunk_tiles)
 };
 
 // the clamped (start, nnew) of sequence b: s0 + n <= L <= Tmax, n <= Tn
@@ -146,7 +180,8 @@ __global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t t
 // occupancy: the 64 instantiation fits two waves per SIMD (171 VGPRs).  Under the same bound the
 // 128 one needs 256 VGPRs and 44 B of scratch per lane (the compiler's resource report), so it is
 // built for one wave per SIMD, where it spills nothing.
-template <int D>
+// SPLIT: a workgroup sweeps one chunk of its query block's tiles and stores fp32 partials (header)
+template <int D, bool SPLIT>
 __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(AppendParams p) {
   static_assert(D == 64 || D == 128, "head dim 64 or 128");
   constexpr int RS = D + 8;                // K image row stride (elements): row reads
@@ -155,9 +190,18 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
   constexpr int NDB = D / 32;              // 32-dim blocks of O
   __shared__ __attribute__((aligned(16))) uint16_t Ks[TILE * RS];
   __shared__ __attribute__((aligned(16))) uint16_t Vs[TILE * RSV];
-  const int BH = gridDim.x / p.nqb;
-  const int bh = blockIdx.x % BH;
-  const int qb = p.nqb - 1 - blockIdx.x / BH;  // the last query block sweeps the most keys: first
+  int BH, bh, qb, ck = 0;
+  if constexpr (SPLIT) {  // (query block, chunk) slowest: the last block first, its chunks from key 0 up
+    BH = gridDim.x / (p.nqb * p.nsplit);
+    bh = blockIdx.x % BH;
+    const int rest = blockIdx.x / BH;
+    ck = rest % p.nsplit;
+    qb = p.nqb - 1 - rest / p.nsplit;
+  } else {
+    BH = gridDim.x / p.nqb;
+    bh = blockIdx.x % BH;
+    qb = p.nqb - 1 - blockIdx.x / BH;  // the last query block sweeps the most keys: first
+  }
   const int b = bh / p.H, hh = bh % p.H;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -174,6 +218,13 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
   const int kh = hh / (p.H / p.Hkv);   // GQA: the key/value head of this query head
   // the workgroup's sweep: up to the tile of its last valid query (none: all padding)
   const int ntiles = qb * BLK < n ? (s0 + min(qb * BLK + BLK - 1, nl)) / TILE + 1 : 0;
+  // this workgroup's tiles [t0, t1): all of them, or chunk ck cut at the block's last tile
+  int t0 = 0, t1 = ntiles;
+  if constexpr (SPLIT) {
+    t0 = ck * p.chunk_tiles;
+    t1 = min(ntiles, t0 + p.chunk_tiles);
+    if (t0 >= ntiles) return;  // uniform in the workgroup, before any barrier: no key of this chunk is visible
+  }
 
   s8v qf[NS];
   {
@@ -219,12 +270,12 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
       load_rows(sv, vbase, k0);
     }
   };
-  load_tile(0);
+  load_tile(t0 * TILE);
   sk.store(Ks, RS, tid);
   sv.store(Vs, RSV, tid);
   __syncthreads();
-  for (int t = 0; t < ntiles; ++t) {
-    if (t + 1 < ntiles) load_tile((t + 1) * TILE);  // issue the next tile's loads now, write them after this tile
+  for (int t = t0; t < t1; ++t) {
+    if (t + 1 < t1) load_tile((t + 1) * TILE);  // issue the next tile's loads now, write them after this tile
     const int k0 = t * TILE;
     // one tile; DIAG = some key of it lies past the wave's first limit (only those pay for compares)
     auto tile_body = [&](auto diag_c) {
@@ -308,13 +359,26 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
         tile_body(std::false_type{});
     }
     __syncthreads();
-    if (t + 1 < ntiles) {
+    if (t + 1 < t1) {
       sk.store(Ks, RS, tid);
       sv.store(Vs, RSV, tid);
       __syncthreads();
     }
   }
-  if (qi < p.Tn) {
+  if constexpr (SPLIT) {
+    // the chunk's partial of a real query that sees a key of this chunk (t0·64 <= lim: its first
+    // tile ran, m is finite and l > 0).  Other lanes hold nothing (or NaN: an empty row's
+    // exp2(-inf + inf)) and store nothing; append_merge_kernel never reads their slots.
+    if (qi < n && lim >= t0 * TILE) {
+      float* wt = p.ws + ((((int64_t)bh * p.nqb + qb) * p.nsplit + ck) * 4 + w) * ((D + 1) * 32);
+      const float inv = 1.f / l;
+#pragma unroll
+      for (int db = 0; db < NDB; ++db)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) wt[(db * 32 + crow(i, h)) * 32 + r] = acc_o[db][i] * inv;
+      if (h == 0) wt[D * 32 + r] = m + __log2f(l);
+    }
+  } else if (qi < p.Tn) {
     uint16_t* orow = p.out + (((int64_t)b * p.Tn + qi) * p.H + hh) * D;
     if (qi < n) {
       const float inv = 1.f / l;
@@ -332,11 +396,90 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
   }
 }
 
+// ============================================================================ merge of the key split
+// workgroup = the 32 queries of one wave tile of one (batch, head); thread = (query r = tid & 31,
+// dim group g = tid >> 5): dims 4·(g + 8j) + [0, 4), j < D/32 — a wave instruction reads two whole
+// 128-B lines of a partial tile, a thread's four dims of a piece become one 8-B store of the row.
+// A query reads the chunks that hold one of its keys, chunk 0 .. lim / (64·chunk_tiles), and no
+// other: those slots were written by this call's append_attn_kernel<D, true> (header).  Fixed
+// order, fp32: bit-reproducible.
+template <int D>
+__global__ __launch_bounds__(NT) void append_merge_kernel(AppendParams p) {
+  constexpr int NP = D / 32;  // 8-B pieces of the row per thread
+  const int BH = gridDim.x / ((p.Tn + 31) / 32);
+  const int bh = blockIdx.x % BH, qt = blockIdx.x / BH;
+  const int b = bh / p.H, hh = bh % p.H;
+  const int r = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const int qi = qt * 32 + r;
+  if (qi >= p.Tn) return;
+  const Span sp = span_of(p, b);
+  uint16_t* orow = p.out + (((int64_t)b * p.Tn + qi) * p.H + hh) * D;
+  if (qi >= sp.n) {  // a padding row: exact zeros
+#pragma unroll
+    for (int j = 0; j < NP; ++j) *reinterpret_cast<uint2*>(orow + 4 * (g + 8 * j)) = make_uint2(0u, 0u);
+    return;
+  }
+  const int nc = min((sp.s0 + qi) / (TILE * p.chunk_tiles) + 1, p.nsplit);
+  constexpr int TS = (D + 1) * 32;  // floats of a wave tile: O^T[D][32], then lse[32]
+  const float* wt = p.ws + ((((int64_t)bh * p.nqb + (qt >> 2)) * p.nsplit) * 4 + (qt & 3)) * TS;
+  float mx = -INFINITY;
+  for (int k = 0; k < nc; ++k) mx = fmaxf(mx, wt[(int64_t)k * 4 * TS + D * 32 + r]);
+  float L = 0.f, O[NP][4] = {};
+  for (int k = 0; k < nc; ++k) {
+    const float* t = wt + (int64_t)k * 4 * TS;
+    const float wgt = exp2f(t[D * 32 + r] - mx);
+    L += wgt;
+#pragma unroll
+    for (int j = 0; j < NP; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) O[j][e] += wgt * t[(4 * (g + 8 * j) + e) * 32 + r];
+  }
+  const float inv = 1.f / L;
+#pragma unroll
+  for (int j = 0; j < NP; ++j)
+    *reinterpret_cast<uint2*>(orow + 4 * (g + 8 * j)) =
+        make_uint2(pack2_bf16(O[j][0] * inv, O[j][1] * inv), pack2_bf16(O[j][2] * inv, O[j][3] * inv));
+}
+
 // ============================================================================ host
+// the key split of a call: nsplit chunks of chunk_tiles 64-key tiles each (nsplit = 1: the unsplit
+// kernel).  key_splits = 1: never; n > 1: n chunks asked for, whatever the thresholds (tests, A/B
+// runs); 0: the plan —
+//   * as many chunks as keep B · H · nqb · nsplit within the workgroups the chip holds at once,
+//     256 CUs x 2 at head dim 64 and x 1 at 128 (the launch bounds above): one more round of
+//     workgroups costs what the split saved (measured at 128, batch 8: 0.76 - 0.93 x);
+//   * at least kMinTiles tiles (256 keys, decode.hip's figure) per chunk, at most kMaxSplit chunks;
+//   * none unless that gives kMinChunks chunks, i.e. from 12 tiles (> 704 keys) on: with two chunks
+//     of a 512-key history the kernels gain 1 us and an eager turn pays 3 us per layer for the
+//     second launch and the workspace.
+// docs/FINDINGS.md §48 has the runs behind these.
+constexpr int64_t kMinTiles = 4, kMinChunks = 3, kMaxSplit = 64;
+struct SplitPlan {
+  int nsplit, chunk_tiles;
+};
+static SplitPlan plan(int64_t BHq, int64_t L, int64_t head_dim, int64_t key_splits) {
+  const int64_t tiles = (L + TILE - 1) / TILE;
+  const int64_t slots = head_dim == 64 ? 512 : 256;
+  int64_t nc = 1;
+  if (key_splits > 1) {
+    nc = std::min(key_splits, tiles);
+  } else if (key_splits == 0 && 2 * BHq <= slots && tiles >= kMinChunks * kMinTiles) {
+    nc = std::min({slots / BHq, tiles / kMinTiles, kMaxSplit});
+  }
+  const int64_t ct = (tiles + nc - 1) / nc;
+  return SplitPlan{(int)((tiles + ct - 1) / ct), (int)ct};
+}
+
+int64_t append_attn_plan(int64_t batch, int64_t n_head, int64_t Tn, int64_t kv_len_max, int64_t head_dim) {
+  TORCH_CHECK(batch >= 1 && n_head >= 1 && Tn >= 1 && kv_len_max >= 1, "append_attn_plan: empty problem");
+  TORCH_CHECK(head_dim == 64 || head_dim == 128, "append_attn_plan: head dim must be 64 or 128, got ", head_dim);
+  return plan(batch * n_head * ((Tn + BLK - 1) / BLK), kv_len_max, head_dim, 0).nsplit;
+}
+
 at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
                            const at::Tensor& start, const at::Tensor& nnew, int64_t n_head, double scale,
                            int64_t kv_len_max, const c10::optional<at::Tensor>& rope_cos,
-                           const c10::optional<at::Tensor>& rope_sin) {
+                           const c10::optional<at::Tensor>& rope_sin, int64_t key_splits) {
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 3 && qkv.stride(2) == 1 &&
                   qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && ((uintptr_t)qkv.data_ptr() & 15) == 0,
               "append_attn: qkv must be a bf16 [B, Tn, (H + 2·Hkv)·D] GPU view, unit last stride, strides multiples "
@@ -367,6 +510,8 @@ at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
               "append_attn: caches must be on qkv's device");
   TORCH_CHECK(kv_len_max >= 1 && kv_len_max <= Tmax, "append_attn: kv_len_max must be in [1, Tmax]");
   TORCH_CHECK(scale > 0, "append_attn: scale must be positive");
+  TORCH_CHECK(key_splits >= 0, "append_attn: key_splits must be 0 (the plan), 1 (never) or a chunk count, got ",
+              key_splits);
   const Rope rp = [&] {
     const bool hc = rope_cos.has_value() && rope_cos->defined(), hs = rope_sin.has_value() && rope_sin->defined();
     TORCH_CHECK(hc == hs, "append_attn: rope_cos and rope_sin go together");
@@ -403,14 +548,33 @@ at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
   p.L = (int)std::min(Tmax, kv_len_max);
   p.nqb = (int)nqb;
   p.sc2 = (float)scale * kLog2e;
+  // host values only (B, H, Tn, kv_len_max, D): the grids and the workspace are the same on every replay of a graph
+  const SplitPlan sp = plan(B * H * nqb, p.L, D, key_splits);
+  p.nsplit = sp.nsplit;
+  p.chunk_tiles = sp.chunk_tiles;
+  p.ws = nullptr;
+  const int64_t nwg = B * H * nqb * sp.nsplit, nmerge = B * H * ((Tn + 31) / 32);
+  TORCH_CHECK(nwg < (1LL << 31) && nmerge < (1LL << 31), "append_attn: grid too large");
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
+  at::Tensor ws;  // allocated like `out`; every slot the merge reads is written by this call first
+  if (sp.nsplit > 1) {
+    ws = at::empty({nwg * 4 * (D + 1) * 32}, qkv.options().dtype(at::kFloat));
+    p.ws = ws.data_ptr<float>();
+  }
   hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   auto launch = [&](auto d_c) {
     constexpr int HD = decltype(d_c)::value;
     hipLaunchKernelGGL(append_kv_kernel<HD>, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, p, total);
     C10_HIP_KERNEL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(append_attn_kernel<HD>, dim3((unsigned)(B * H * nqb)), dim3(NT), 0, st, p);
-    C10_HIP_KERNEL_LAUNCH_CHECK();
+    if (sp.nsplit == 1) {
+      hipLaunchKernelGGL((append_attn_kernel<HD, false>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+    } else {
+      hipLaunchKernelGGL((append_attn_kernel<HD, true>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+      hipLaunchKernelGGL(append_merge_kernel<HD>, dim3((unsigned)nmerge), dim3(NT), 0, st, p);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+    }
   };
   if (D == 64)
     launch(std::integral_constant<int, 64>{});
@@ -423,3 +587,4 @@ at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
 }  // namespace nbd
 
 TORCH_LIBRARY_IMPL(nbd, CUDA, m) { m.impl("append_attn", &nbd::attn::append_attn_hip); }
+TORCH_LIBRARY_IMPL(nbd, CompositeExplicitAutograd, m) { m.impl("append_attn_plan", &nbd::attn::append_attn_plan); }

@@ -29,7 +29,9 @@ TORCH_LIBRARY(nbd, m) {
         "Tensor? rope_sin, Tensor partials) -> Tensor");
   // a block of new tokens per sequence over the cache (csrc/kernels/append.hip): k | v appended at start[b] + i
   m.def("append_attn(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor start, Tensor nnew, int n_head, "
-        "float scale, int kv_len_max, Tensor? rope_cos, Tensor? rope_sin) -> Tensor");
+        "float scale, int kv_len_max, Tensor? rope_cos, Tensor? rope_sin, int key_splits=0) -> Tensor");
+  // the key chunks append_attn's plan (key_splits = 0) takes for this problem; 1 = the unsplit kernel
+  m.def("append_attn_plan(int batch, int n_head, int Tn, int kv_len_max, int head_dim) -> int");
   m.def("greedy_advance(Tensor logits, Tensor(a!) tok, Tensor(b!) pos, Tensor(c!) out, Tensor(d!)? done, int eos) -> ()");
   m.def("linear_small(Tensor x, Tensor w, Tensor? bias, Tensor? norm_w, Tensor? norm_b, float eps, int norm, "
         "int act, Tensor? residual) -> Tensor");

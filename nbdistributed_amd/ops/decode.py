@@ -12,6 +12,7 @@ head dim 64 or 128).
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 from ._lib import _require
@@ -288,8 +289,34 @@ def append_attention_reference(qkv, k_cache, v_cache, start, nnew, n_head: int, 
     return o.masked_fill(~valid[:, :, None], 0.0).to(qkv.dtype)
 
 
+def _append_split_default(value: Optional[str]) -> int:
+    """``NBD_APPEND_SPLIT`` as the op's ``key_splits``: unset / ``auto`` → 0 (the kernel's plan decides),
+    ``0`` → 1 (never split), an integer n → n chunks."""
+    v = (value or "auto").strip().lower()
+    if v == "auto":
+        return 0
+    n = int(v)
+    if n < 0:
+        raise ValueError(f"NBD_APPEND_SPLIT must be auto, 0 or a chunk count, got {value!r}")
+    return max(n, 1)
+
+
+# what ``append_attention(key_splits=None)`` passes to the kernel: 0 = its plan, 1 = never split, n = n chunks
+APPEND_KEY_SPLITS = _append_split_default(os.environ.get("NBD_APPEND_SPLIT"))
+
+
+def append_key_splits(batch: int, n_head: int, Tn: int, kv_len_max: int, head_dim: int = 64) -> int:
+    """The key chunks the block-append kernel's plan takes for this problem (1 = the unsplit kernel):
+    it splits over keys when the history is long (> 512 keys) and ``batch · n_head · ⌈Tn / 128⌉``
+    workgroups would leave most of the chip idle.  The same C++ function the op consults."""
+    _require()
+    import torch
+
+    return int(torch.ops.nbd.append_attn_plan(int(batch), int(n_head), int(Tn), int(kv_len_max), int(head_dim)))
+
+
 def append_attention(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Optional[float] = None, rope=None,
-                     kv_len_max: Optional[int] = None):
+                     kv_len_max: Optional[int] = None, key_splits: Optional[int] = None):
     """Attention of a block of new tokens per sequence over its KV cache (multi-turn append).
 
     ``qkv`` [B, Tn, (H + 2·Hkv)·D] is the new tokens' packed projection (any ``Tn`` ≥ 1: the kernel
@@ -299,7 +326,10 @@ def append_attention(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Opt
     start[b] + i when ``rope`` = (cos, sin) tables) and v are written to cache row start[b] + i and
     query i attends rows 0..start[b] + i; no later row influences it, whatever it holds, and rows
     ≥ start[b] + nnew[b] are not written.  ``kv_len_max`` is a host bound on max(start + nnew)
-    (default Tmax).  Returns [B, Tn, H·D] with exact zeros on the padding rows.  GPU bf16 (qkv and
+    (default Tmax).  ``key_splits``: 0 = the kernel's plan splits the sweep over keys into chunks
+    when that fills the chip (:func:`append_key_splits`), 1 = never, n > 1 = n chunks whatever the
+    plan says; ``None`` = ``APPEND_KEY_SPLITS`` (``NBD_APPEND_SPLIT``: ``auto`` | ``0`` never | n); the
+    PyTorch path ignores it.  Returns [B, Tn, H·D] with exact zeros on the padding rows.  GPU bf16 (qkv and
     caches), head dim 64 or 128 (the caches' last dim; ``rope`` tables [≥ Tmax, D/2]) →
     ``csrc/kernels/append.hip``; elsewhere — CPU, other dtypes, other head dims — the same math in
     PyTorch (:func:`append_attention_reference`)."""
@@ -314,7 +344,8 @@ def append_attention(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Opt
         if qkv.stride(-1) != 1 or qkv.stride(0) % 8 or qkv.stride(1) % 8 or qkv.data_ptr() % 16:
             qkv = qkv.contiguous()
         return torch.ops.nbd.append_attn(qkv, k_cache, v_cache, start, nnew, int(n_head), sc,
-                                         int(kv_len_max or Tmax), cos, sin)
+                                         int(kv_len_max or Tmax), cos, sin,
+                                         int(APPEND_KEY_SPLITS if key_splits is None else key_splits))
     return append_attention_reference(qkv, k_cache, v_cache, start, nnew, n_head, sc, rope, kv_len_max)
 
 
