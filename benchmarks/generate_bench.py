@@ -54,6 +54,13 @@ to the first token of turn 2 (SmolLM2-135M, or the head-dim-128 stack), same poi
 
     python benchmarks/generate_bench.py --continue --split [--head-dim 128] [--layers 4] [--batches 1,8]
         [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
+
+``--continue --kv-dtype fp8 [--head-dim 128]``: continuing from an fp8 cache against the bf16 cache,
+rounds interleaved: ``ops.append_attention`` alone and the time to the first token of turn 2, same
+points; cache bytes derived from the shapes.
+
+    python benchmarks/generate_bench.py --continue --kv-dtype fp8 [--head-dim 128] [--layers 4] [--batches 1,8]
+        [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -686,6 +693,113 @@ def split_bench(a):
             json.dump(res, f, indent=1)
 
 
+def kv8_continue_bench(a):
+    """``--continue --kv-dtype fp8`` (with ``--head-dim 128``: the Llama-3.2-3B-shaped stack, else
+    SmolLM2-135M): continuing from an fp8 cache against the bf16 cache, rounds interleaved in one
+    process.  Per (batch, history, turn): ``ops.append_attention`` alone (all its launches, the
+    kernel's own plan) and the time to the first token of turn 2.  Cache bytes are derived from the
+    shapes.  No ratio is a target: a point where fp8 is slower is reported as it comes out."""
+    import statistics
+
+    from nbdistributed_amd import ops
+    from nbdistributed_amd.generation import generate
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+    from nbdistributed_amd.ops.decode import q8
+
+    D = a.head_dim or 64
+    hists = [int(x) for x in a.hist.split(",")]
+    turns = [int(x) for x in a.turn.split(",")]
+    batches = [int(x) for x in a.batches.split(",")]
+    arms = ("bf16", "fp8")
+
+    def row_of(t, **key):
+        row = dict(key)
+        for name in arms:
+            row[name], row[name + "_min_max"] = round(statistics.median(t[name]), 3), [round(min(t[name]), 3), round(max(t[name]), 3)]
+        row["bf16_over_fp8"] = round(statistics.median([x / y for x, y in zip(t["bf16"], t["fp8"])]), 3)
+        spread = max(t["bf16"]) - min(t["bf16"])
+        row["fp8_slower"] = bool(statistics.median(t["fp8"]) > statistics.median(t["bf16"]) + spread)
+        print(json.dumps(row), flush=True)
+        return row
+
+    res = {"what": f"continuing from an fp8 KV cache vs the bf16 cache at head dim {D}, rounds interleaved; kernel = us per "
+                   f"ops.append_attention call (key_splits = the plan), points = ms to the first token of turn 2 (eager)",
+           "rounds": a.rounds, "kernel": [], "points": []}
+    H, Hkv = (24, 8) if D == 128 else (9, 3)
+    n = 20
+    for B in batches:
+        for hist in hists:
+            for turn in turns:
+                Tn, Tmax = turn + 1, -(-(hist + max(turns) + 2) // 128) * 128
+                k16 = torch.randn(B, Hkv, Tmax, D, device="cuda").to(torch.bfloat16)
+                v16 = torch.randn(B, Hkv, Tmax, D, device="cuda").to(torch.bfloat16)
+                caches = {"bf16": (k16, v16), "fp8": (q8(k16), q8(v16))}
+                qkv = torch.randn(B, Tn, (H + 2 * Hkv) * D, device="cuda").to(torch.bfloat16)
+                st = torch.full((B,), hist - 1, device="cuda", dtype=torch.int64)
+                nn = torch.full((B,), Tn, device="cuda", dtype=torch.int64)
+                rope = ops.rope_tables(Tmax, D, 10000.0, "cuda")
+                f = lambda name: ops.append_attention(qkv, *caches[name], st, nn, H, rope=rope, kv_len_max=hist + Tn)  # noqa: E731
+                for name in arms:
+                    assert ops.append_supported(qkv, *caches[name][:1], H, caches[name][1])
+                    for _ in range(3):
+                        f(name)
+                torch.cuda.synchronize()
+                us = {name: [] for name in arms}
+                for _ in range(a.rounds):
+                    for name in arms:
+                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        s.record()
+                        for _ in range(n):
+                            f(name)
+                        e.record()
+                        e.synchronize()
+                        us[name].append(s.elapsed_time(e) / n * 1e3)
+                res["kernel"].append(row_of(us, B=B, H=H, Hkv=Hkv, history=hist, Tn=Tn,
+                                            key_splits=ops.append_key_splits(B, H, Tn, hist + Tn, D),
+                                            cache_rows_bytes={x: 2 * B * Hkv * (hist + Tn) * D * caches[x][0].element_size()
+                                                              for x in arms}))
+    torch.manual_seed(0)
+    if D == 128:
+        vocab = 32000
+        cfg = LlamaConfig(vocab_size=vocab, hidden_size=3072, intermediate_size=8192, num_hidden_layers=a.layers,
+                          num_attention_heads=24, num_key_value_heads=8, max_position_embeddings=8192, explicit_head_dim=D)
+        m = LlamaForCausalLM(cfg).to("cuda", torch.bfloat16).eval()
+    else:
+        m, vocab, _, _ = _bench_model("smollm2", max(hists) + max(turns) + 2)
+    for B in batches:
+        for hist in hists:
+            ids = torch.randint(1, vocab, (B, hist - 8), device="cuda")
+            t_max = -(-(hist + max(turns) + 2) // 128) * 128
+            held = {name: generate(m, ids, 8, t_max=t_max, graph=False, return_cache=True,
+                                   kv_dtype=None if name == "bf16" else "fp8")[1] for name in arms}
+            state = {name: (c.lengths.clone(), c.pending.clone()) for name, c in held.items()}
+            for turn in turns:
+                new = torch.randint(1, vocab, (B, turn), device="cuda")
+
+                def cont(name):
+                    c = held[name]
+                    c.lengths, c.pending = state[name][0].clone(), state[name][1].clone()
+                    return generate(m, new, 1, cache=c, graph=False)
+
+                first = {name: cont(name)[:, -1] for name in arms}  # (also the warm-up of both arms)
+                ms = {name: [] for name in arms}
+                for _ in range(a.rounds):
+                    for name in arms:
+                        torch.cuda.synchronize()
+                        t = time.perf_counter()
+                        cont(name)
+                        torch.cuda.synchronize()
+                        ms[name].append((time.perf_counter() - t) * 1e3)
+                res["points"].append(row_of(ms, batch=B, history=hist, turn=turn,
+                                            cache_bytes={x: held[x].nbytes for x in arms},
+                                            first_token_same=bool((first["bf16"] == first["fp8"]).all())))
+            del held
+            torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--head-dim", dest="head_dim", type=int, default=0, choices=[0, 128],
@@ -718,6 +832,10 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.kv_dtype and a.cont:
+        if a.batches == "1,8,32":
+            a.batches = "1,8"
+        return kv8_continue_bench(a)
     if a.split and a.cont:
         if a.batches == "1,8,32":
             a.batches = "1,8"

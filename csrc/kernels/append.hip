@@ -71,6 +71,31 @@
 //     <64, true> 171 / 0 / 0 / 2 / 21 504, <128, false> 256 / 131 / 0 / 1 / 37 888, <128, true>
 //     256 / 133 / 0 / 1 / 37 888; merge 52 (64) and 90 (128) VGPR, no LDS.
 //
+// fp8 caches (append_kv_kernel<D, true>, append_attn_kernel<D, SPLIT, true>; the row format is
+// kv8.h's, decode.hip's contract: D bytes of OCP e4m3fn per row, no scales, q8 of the bf16 row):
+//   * append_kv_kernel rotates k in fp32 and packs it to bf16 as before, then quantises each 8-dim
+//     chunk (quant8: clamp to ±448, round to nearest even, NaN kept) and stores 8 B; v is quantised
+//     from the bf16 row of qkv.  The rotated k is rounded fp32 -> bf16 -> e4m3, like a prefilled row.
+//   * append_attn_kernel dequantises while it stages, not at the MFMA: a tile's rows are loaded as
+//     8-B pieces, one per ld16 of the bf16 kernel, with the same thread-to-element mapping
+//     (StagePair8, StageRows8<D>); a tile is one contiguous 4 KiB / 8 KiB run per (batch, kv head).
+//     The pieces stay e4m3 in registers while the loads are in flight under the current tile's
+//     math — half the staging registers — and become bf16 only at the ds_write (widen8:
+//     v_cvt_pk_f32_fp8, then the high halves of the two fp32 values in one v_perm_b32; every e4m3
+//     value is exact in bf16).  Rows >= kend become zero bytes on the row index, before the
+//     conversion.  LDS images, reads, MFMA body, softmax, diagonal, partials and sweep bounds are
+//     the bf16 kernel's: the output is bit for bit what <D, SPLIT, false> gives on a bf16 cache
+//     holding the dequantised rows (tests/test_gpu_append_kv8.py), split and unsplit.
+//   * not built: an fp8 MFMA path (q and P are bf16; quantising them changes the result) and e4m3
+//     LDS images converted at every wave's read (four times the conversions, a second transposed
+//     read layout).
+//   * the <.., false> instantiations and both merge kernels are, instruction for instruction, what
+//     they were (compared in the ISA).  The new ones, VGPR / AGPR / scratch / waves per SIMD / LDS:
+//     attn <64, false, true> 163 / 0 / 0 / 3 / 21 504, <64, true, true> 165 / 0 / 0 / 3 / 21 504,
+//     <128, false, true> 243 / 128 / 0 / 1 / 37 888, <128, true, true> 245 / 128 / 0 / 1 / 37 888
+//     (the launch bounds are the bf16 kernels'); append_kv <64 | 128, true> 50 VGPR (bf16: 49).
+//     No packed fp32 instruction in the unit, with -fno-slp-vectorize as it is built.
+//
 // Head dim: both kernels take it as a template parameter, D = 64 | 128 (the host reads it from the
 // caches' last dim); "64" above stands for D.  The algorithm is the same; what follows D:
 //   * a lane holds D/16 query fragments, S takes D/16 MFMA k-steps per 32-key block, O is D/32
@@ -108,6 +133,7 @@
 #include <type_traits>
 
 #include "attn_common.h"
+#include "kv8.h"
 #include "nbd_common.h"
 
 namespace nbd {
@@ -116,7 +142,7 @@ namespace attn {
 struct AppendParams {
   const uint16_t* qkv;  // [B, Tn, (H + 2·Hkv)·D] bf16, element strides sb / st, unit last stride
   int64_t sb, st;
-  uint16_t* kc;  // [B, Hkv, Tmax, D] bf16, contiguous
+  uint16_t* kc;  // [B, Hkv, Tmax, D] contiguous: bf16, or e4m3fn bytes (the <.., F8 = true> kernels)
   uint16_t* vc;
   const int64_t* start;  // [B]
   const int64_t* nnew;   // [B]
@@ -147,10 +173,41 @@ __device__ __forceinline__ s8v zero8() {
   return z;
 }
 
+// ---- fp8 caches: a thread's 8 dims of a row are 8 B (kv8.h)
+__device__ __forceinline__ u32x2 ld8(const uint8_t* p) { return *reinterpret_cast<const u32x2*>(p); }
+__device__ __forceinline__ void st8(uint8_t* p, u32x2 v) { *reinterpret_cast<u32x2*>(p) = v; }
+__device__ __forceinline__ u32x2 quant8(s8v v) { return nbd::quant8(__builtin_bit_cast(u32x4, v)); }
+__device__ __forceinline__ s8v widen8s(u32x2 v) { return __builtin_bit_cast(s8v, widen8(v)); }
+
+// StagePair and StageRows<D> (attn_common.h; StageRows<64> is Stage2's mapping) over e4m3 pieces:
+// the same thread-to-element mapping, half the registers while the loads are in flight, expanded
+// to bf16 (widen8: exact) at the ds_write — the LDS images are the bf16 kernel's, byte for byte
+struct StagePair8 {
+  u32x2 a, b;
+  __device__ __forceinline__ void store(uint16_t* lds, int stride, int tid) const {
+    uint16_t* p = lds + (tid >> 2) * stride + (tid & 3) * 8;
+    st16(p, widen8s(a));
+    st16(p + 32, widen8s(b));
+  }
+};
+template <int D>
+struct StageRows8 {
+  u32x2 a[D / 32];
+  __device__ __forceinline__ void store(uint16_t* lds, int stride, int tid) const {
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+      const int c = tid + i * NT;
+      st16(lds + (c >> (D == 64 ? 3 : 4)) * stride + (c & (D / 8 - 1)) * 8, widen8s(a[i]));
+    }
+  }
+};
+
 // ============================================================================ cache append
 // thread = (b, i, kv head, c), c < D/16: dims [8c, 8c + 8) and their rotation partners
-// [D/2 + 8c, D/2 + 8c + 8) of k, the same two 16-B chunks of v
-template <int D>
+// [D/2 + 8c, D/2 + 8c + 8) of k, the same two 16-B chunks of v.  F8: each chunk is stored as its 8
+// e4m3 bytes, q8 of the bf16 chunk — the rotated k is rounded fp32 -> bf16 -> e4m3, like a
+// prefilled row and like decode.hip's
+template <int D, bool F8>
 __global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t total) {
   static_assert(D == 64 || D == 128, "head dim 64 or 128");
   constexpr int HALF = D / 2;
@@ -170,10 +227,19 @@ __global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t t
   s8v ka = ld16(ks), kb = ld16(ks + HALF);
   if (p.rp.cos != nullptr) rope8_hd<HALF>(ka, kb, p.rp, t, c * 8);
   const int64_t dst = (((int64_t)b * p.Hkv + kvh) * p.Tmax + t) * D + c * 8;
-  st16(p.kc + dst, ka);
-  st16(p.kc + dst + HALF, kb);
-  st16(p.vc + dst, ld16(vs));
-  st16(p.vc + dst + HALF, ld16(vs + HALF));
+  if constexpr (F8) {  // dst counts elements: bytes here
+    uint8_t* const k8 = reinterpret_cast<uint8_t*>(p.kc) + dst;
+    uint8_t* const v8 = reinterpret_cast<uint8_t*>(p.vc) + dst;
+    st8(k8, quant8(ka));
+    st8(k8 + HALF, quant8(kb));
+    st8(v8, quant8(ld16(vs)));
+    st8(v8 + HALF, quant8(ld16(vs + HALF)));
+  } else {
+    st16(p.kc + dst, ka);
+    st16(p.kc + dst + HALF, kb);
+    st16(p.vc + dst, ld16(vs));
+    st16(p.vc + dst + HALF, ld16(vs + HALF));
+  }
 }
 
 // ============================================================================ attention
@@ -181,7 +247,8 @@ __global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t t
 // 128 one needs 256 VGPRs and 44 B of scratch per lane (the compiler's resource report), so it is
 // built for one wave per SIMD, where it spills nothing.
 // SPLIT: a workgroup sweeps one chunk of its query block's tiles and stores fp32 partials (header)
-template <int D, bool SPLIT>
+// F8: the caches hold e4m3 bytes; only load_tile and the staging structs differ (header)
+template <int D, bool SPLIT, bool F8>
 __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(AppendParams p) {
   static_assert(D == 64 || D == 128, "head dim 64 or 128");
   constexpr int RS = D + 8;                // K image row stride (elements): row reads
@@ -236,11 +303,14 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
   f16x acc_o[NDB] = {};
   float m = -INFINITY, l = 0.f;
 
-  const uint16_t* kbase = p.kc + ((int64_t)b * p.Hkv + kh) * p.Tmax * D;
-  const uint16_t* vbase = p.vc + ((int64_t)b * p.Hkv + kh) * p.Tmax * D;
+  // (F8: a row is D bytes, so the head's first row sits at half this element offset)
+  const int64_t hoff = ((int64_t)b * p.Hkv + kh) * p.Tmax * (F8 ? D / 2 : D);
+  const uint16_t* kbase = p.kc + hoff;
+  const uint16_t* vbase = p.vc + hoff;
   // the 64 tile keeps the fixed staging structs, so that instantiation stays the kernel it was
-  std::conditional_t<D == 64, StagePair, StageRows<D>> sk;
-  std::conditional_t<D == 64, Stage2, StageRows<D>> sv;
+  std::conditional_t<F8, std::conditional_t<D == 64, StagePair8, StageRows8<D>>,
+                     std::conditional_t<D == 64, StagePair, StageRows<D>>> sk;
+  std::conditional_t<F8, StageRows8<D>, std::conditional_t<D == 64, Stage2, StageRows<D>>> sv;
   // a tile's rows from the cache (row index clamped into it); rows >= kend become zeros
   auto load_rows = [&](StageRows<D>& sr, const uint16_t* base, int k0) {  // (128)
 #pragma unroll
@@ -251,8 +321,31 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
       if (vr >= kend) sr.a[i] = zero8();
     }
   };
+  // F8: the same rows as 8-B pieces, one per ld16 of the bf16 tile; the row index decides on the
+  // zeros before anything is converted, so a NaN byte of a free row never reaches LDS
+  auto load_rows8 = [&](StageRows8<D>& sr, const uint16_t* base, int k0) {
+    const uint8_t* const base8 = reinterpret_cast<const uint8_t*>(base);
+#pragma unroll
+    for (int i = 0; i < D / 32; ++i) {
+      const int c = tid + i * NT;
+      const int vr = k0 + (c >> (D == 64 ? 3 : 4));
+      sr.a[i] = ld8(base8 + (int64_t)min(vr, p.Tmax - 1) * D + (c & (D / 8 - 1)) * 8);
+      if (vr >= kend) sr.a[i] = u32x2{0u, 0u};
+    }
+  };
   auto load_tile = [&](int k0) {
-    if constexpr (D == 64) {
+    if constexpr (F8) {
+      if constexpr (D == 64) {  // StagePair's mapping: row tid / 4, pieces q and q + 4
+        const int kr = k0 + (tid >> 2);
+        const uint8_t* pk = reinterpret_cast<const uint8_t*>(kbase) + (int64_t)min(kr, p.Tmax - 1) * D + (tid & 3) * 8;
+        sk.a = ld8(pk);
+        sk.b = ld8(pk + 32);
+        if (kr >= kend) sk.a = sk.b = u32x2{0u, 0u};
+      } else {
+        load_rows8(sk, kbase, k0);
+      }
+      load_rows8(sv, vbase, k0);
+    } else if constexpr (D == 64) {
       const int kr = k0 + (tid >> 2);
       const uint16_t* pk = kbase + (int64_t)min(kr, p.Tmax - 1) * D + (tid & 3) * 8;
       sk.a = ld16(pk);
@@ -452,7 +545,10 @@ __global__ __launch_bounds__(NT) void append_merge_kernel(AppendParams p) {
 //   * none unless that gives kMinChunks chunks, i.e. from 12 tiles (> 704 keys) on: with two chunks
 //     of a 512-key history the kernels gain 1 us and an eager turn pays 3 us per layer for the
 //     second launch and the workspace.
-// docs/FINDINGS.md §48 has the runs behind these.
+// docs/FINDINGS.md §48 has the runs behind these.  fp8 caches take the same plan: the thresholds
+// were measured on bf16 bytes, and how the fp8 kernel's time divides between the streamed bytes
+// (half) and the MFMA / conversion work (more) is not known well enough to move them — a change
+// here wants an interleaved A/B of its own.
 constexpr int64_t kMinTiles = 4, kMinChunks = 3, kMaxSplit = 64;
 struct SplitPlan {
   int nsplit, chunk_tiles;
@@ -484,11 +580,21 @@ at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
                   qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && ((uintptr_t)qkv.data_ptr() & 15) == 0,
               "append_attn: qkv must be a bf16 [B, Tn, (H + 2·Hkv)·D] GPU view, unit last stride, strides multiples "
               "of 8 elements, 16-B aligned");
-  TORCH_CHECK(k_cache.is_cuda() && k_cache.scalar_type() == at::kBFloat16 && k_cache.is_contiguous() &&
-                  k_cache.dim() == 4 && v_cache.dim() == 4 && v_cache.is_cuda() &&
-                  v_cache.scalar_type() == at::kBFloat16 && v_cache.is_contiguous() &&
-                  ((uintptr_t)k_cache.data_ptr() & 15) == 0 && ((uintptr_t)v_cache.data_ptr() & 15) == 0,
-              "append_attn: caches must be contiguous bf16 [B, Hkv, Tmax, D]");
+  const bool f8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(), "append_attn: k_cache (", k_cache.scalar_type(),
+              ") and v_cache (", v_cache.scalar_type(), ") must have the same dtype, bf16 or float8_e4m3fn");
+  if (f8) {
+    TORCH_CHECK(k_cache.is_cuda() && k_cache.is_contiguous() && k_cache.dim() == 4 && v_cache.dim() == 4 &&
+                    v_cache.is_cuda() && v_cache.is_contiguous() && ((uintptr_t)k_cache.data_ptr() & 7) == 0 &&
+                    ((uintptr_t)v_cache.data_ptr() & 7) == 0,
+                "append_attn: fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, D], 8-B aligned rows");
+  } else {
+    TORCH_CHECK(k_cache.is_cuda() && k_cache.scalar_type() == at::kBFloat16 && k_cache.is_contiguous() &&
+                    k_cache.dim() == 4 && v_cache.dim() == 4 && v_cache.is_cuda() &&
+                    v_cache.scalar_type() == at::kBFloat16 && v_cache.is_contiguous() &&
+                    ((uintptr_t)k_cache.data_ptr() & 15) == 0 && ((uintptr_t)v_cache.data_ptr() & 15) == 0,
+                "append_attn: caches must be contiguous bf16 [B, Hkv, Tmax, D]");
+  }
   const int64_t D = k_cache.size(3);  // (hides attn::D: the head dim of this call)
   TORCH_CHECK(D == 64 || D == 128, "append_attn: head dim must be 64 or 128, got ", D, " (the caches' last dim)");
   TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "append_attn: k_cache ", k_cache.sizes(), " and v_cache ",
@@ -562,24 +668,32 @@ at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
     p.ws = ws.data_ptr<float>();
   }
   hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  auto launch = [&](auto d_c) {
+  auto launch = [&](auto d_c, auto f8_c) {
     constexpr int HD = decltype(d_c)::value;
-    hipLaunchKernelGGL(append_kv_kernel<HD>, dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, p, total);
+    constexpr bool F8 = decltype(f8_c)::value;
+    hipLaunchKernelGGL((append_kv_kernel<HD, F8>), dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, p, total);
     C10_HIP_KERNEL_LAUNCH_CHECK();
     if (sp.nsplit == 1) {
-      hipLaunchKernelGGL((append_attn_kernel<HD, false>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
+      hipLaunchKernelGGL((append_attn_kernel<HD, false, F8>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
-      hipLaunchKernelGGL((append_attn_kernel<HD, true>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
+      hipLaunchKernelGGL((append_attn_kernel<HD, true, F8>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
       C10_HIP_KERNEL_LAUNCH_CHECK();
-      hipLaunchKernelGGL(append_merge_kernel<HD>, dim3((unsigned)nmerge), dim3(NT), 0, st, p);
+      hipLaunchKernelGGL(append_merge_kernel<HD>, dim3((unsigned)nmerge), dim3(NT), 0, st, p);  // fp32 partials only
       C10_HIP_KERNEL_LAUNCH_CHECK();
     }
   };
-  if (D == 64)
-    launch(std::integral_constant<int, 64>{});
-  else
-    launch(std::integral_constant<int, 128>{});
+  if (D == 64) {
+    if (f8)
+      launch(std::integral_constant<int, 64>{}, std::true_type{});
+    else
+      launch(std::integral_constant<int, 64>{}, std::false_type{});
+  } else {
+    if (f8)
+      launch(std::integral_constant<int, 128>{}, std::true_type{});
+    else
+      launch(std::integral_constant<int, 128>{}, std::false_type{});
+  }
   return out;
 }
 

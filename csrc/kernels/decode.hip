@@ -29,7 +29,8 @@
 // the loads and the one store differ: a lane holds its 8 dims as 8 B, a lane group covers one 64-B
 // row, one wave instruction reads 512 contiguous bytes; v_cvt_pk_f32_fp8 unpacks into the same fp32
 // lanes.  The new token's register copy is the stored bytes, so it attends to its own key and
-// value as every later step will read them.
+// value as every later step will read them.  The row format and its helpers (unpack8, quant8,
+// Row<F8>) are kv8.h's, shared with append.hip.
 //
 // A shared prefix (`decode_kernel<G, F8, true>`, op `decode_attn_shared`): several samples of one
 // prompt.  Sequence s of S = B·group belongs to prompt s / group; its logical key j is row j of that
@@ -59,6 +60,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "kv8.h"
 #include "nbd_common.h"
 
 namespace nbd {
@@ -110,65 +112,11 @@ __device__ __forceinline__ float sum_group(float v) {
   return v;
 }
 
-__device__ __forceinline__ void unpack8(const u32x4& w, float (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(w[j] << 16);
-    v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-  }
-}
-
 __device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
   u32x4 w;
 #pragma unroll
   for (int j = 0; j < 4; ++j) w[j] = pack2_bf16(v[2 * j], v[2 * j + 1]);
   return w;
-}
-
-// a lane's 8 dims of a cache row: 16 B of bf16 or 8 B of e4m3fn; either way a row is D/8 of them
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-template <bool F8>
-struct Row {
-  using type = u32x4;
-};
-template <>
-struct Row<true> {
-  using type = u32x2;
-};
-
-__device__ __forceinline__ void unpack8(const u32x2& w, float (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], false);  // bytes 0, 1
-    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[j], true);   // bytes 2, 3
-    v[4 * j] = lo[0];
-    v[4 * j + 1] = lo[1];
-    v[4 * j + 2] = hi[0];
-    v[4 * j + 3] = hi[1];
-  }
-}
-
-// q8 of 8 bf16 values: clamp to ±448 (±inf saturates; e4m3fn has no inf), round to nearest even.
-// NaN is kept out of the clamp (fminf / fmaxf — v_min / v_max / v_med3 — return the other operand)
-// and its byte is written here, 0x7f with the sign: what a cast makes of NaN is then no question.
-__device__ __forceinline__ u32x2 quant8(const u32x4& w) {
-  float f[8];
-  unpack8(w, f);
-  float c[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) c[e] = f[e] != f[e] ? 0.f : fminf(fmaxf(f[e], -448.f), 448.f);
-  u32x2 r;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    int x = 0;
-    x = __builtin_amdgcn_cvt_pk_fp8_f32(c[4 * j], c[4 * j + 1], x, false);
-    x = __builtin_amdgcn_cvt_pk_fp8_f32(c[4 * j + 2], c[4 * j + 3], x, true);
-    r[j] = (uint32_t)x;
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e)
-    if (f[e] != f[e]) r[e >> 2] |= (0x7fu | (__float_as_uint(f[e]) >> 31 << 7)) << (8 * (e & 3));
-  return r;
 }
 
 // HF rotate_half RoPE on this lane's 8 dims [8·d8, 8·d8+8); the partner dims (±D/2) sit in lane

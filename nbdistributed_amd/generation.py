@@ -53,7 +53,8 @@ class KVCache:
 
     ``dtype=torch.float8_e4m3fn``: rows are stored as ``ops.decode.q8`` makes them (clamped to
     ±448, round to nearest even, no scales) by ``store`` and by ``attend`` alike: half the bytes
-    held and half the bytes a decode step streams.  ``extend`` (continue) takes no fp8 cache."""
+    held and half the bytes a decode step or a continued turn streams.  ``extend`` (continue) takes
+    an fp8 cache on a GPU (the block-append kernel's fp8 variant); on the CPU it refuses one."""
 
     def __init__(self, n_layer: int, batch: int, n_head: int, n_kv: int, t_max: int, head_dim: int,
                  dtype=torch.bfloat16, device="cuda"):
@@ -114,10 +115,11 @@ class KVCache:
     def extend(self, layer: int, qkv: torch.Tensor, start: torch.Tensor, nnew: torch.Tensor, rope=None,
                scale=None) -> torch.Tensor:
         """Continue: append the ``nnew[b]`` real rows of ``qkv`` [B, Tn, W] at ``start[b]`` and attend
-        each over the cache up to itself (``ops.append_attention``)."""
+        each over the cache up to itself (``ops.append_attention``).  An fp8 cache is continued on a
+        GPU only, for now: a CPU one raises ``NotImplementedError``."""
         from . import ops
 
-        if self.is_fp8:
+        if self.is_fp8 and not self.k.is_cuda:
             raise NotImplementedError("KVCache.extend: continuing from an fp8 cache is not implemented "
                                       "(the block-append kernel reads bf16 caches only)")
         return ops.append_attention(qkv, self.k[layer], self.v[layer], start, nnew, self.n_head, scale=scale,
@@ -294,9 +296,10 @@ def _run_decode(loop: _DecodeLoop, n: int, graph: bool, key_bound: int, eos_toke
 def _continue(model, input_ids, max_new_tokens: int, cache: KVCache, lengths, sampling: dict, eos_token_id,
               pad_token_id: int, graph, sync_every: int):
     """``generate`` from a returned cache: the block ``[cache.pending, turn…]`` per sequence goes
-    through ``model.extend`` at ``start = cache.lengths``, then the decode loop takes over."""
-    if cache.is_fp8:
-        # the block-append kernel reads bf16 caches only: refuse before any work
+    through ``model.extend`` at ``start = cache.lengths``, then the decode loop takes over.  The
+    cache carries its dtype: an fp8 cache is extended and decoded as fp8 (a GPU feature for now)."""
+    if cache.is_fp8 and not cache.k.is_cuda:
+        # the fp8 block append exists as a HIP kernel only: refuse before any work
         raise NotImplementedError("generate: continuing from an fp8 cache (kv_dtype='fp8') is not implemented; "
                                   "generate the first turn with the default kv_dtype to continue from its cache")
     if max_new_tokens <= 0:
@@ -442,8 +445,12 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
     ``kv_dtype`` = ``"fp8"`` (or ``torch.float8_e4m3fn``) keeps the KV cache in OCP e4m3 without
     scales — each row clamped to ±448 and rounded to nearest even from the bf16 row the default
     cache would hold, by prefill and decode alike — for half the cache bytes held and streamed per
-    token; ``None`` (default) keeps the model's dtype.  A cache of fp8 rows cannot be continued
-    (``cache=`` raises ``NotImplementedError``).
+    token; ``None`` (default) keeps the model's dtype.  With ``cache=`` the cache carries its dtype
+    and ``kv_dtype`` is not needed: an fp8 cache on a GPU is continued as fp8 (the block-append
+    kernel stores the turn's rows quantised and the decode loop goes on over the same cache),
+    ``kv_dtype="fp8"`` beside it is accepted, and a ``kv_dtype`` that contradicts the cache is a
+    ``ValueError``.  fp8 continuation is a GPU feature for now: an fp8 cache on the CPU raises
+    ``NotImplementedError``.
 
     ``num_return_sequences`` = R > 1 draws R samples of every prompt (``temperature`` > 0): the B
     prompts are prefilled once into a ``SharedPrefixKVCache`` that holds each prompt once and R
@@ -471,6 +478,9 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
                                        pad_token_id, graph, t_max, sync_every, kv_dtype)
         return (out, shared) if return_cache else out
     if cache is not None:
+        if kv_dtype is not None and not cache.is_fp8:
+            raise ValueError(f"generate: kv_dtype='fp8' contradicts cache=, which holds {cache.k.dtype} rows (a "
+                             f"cache carries its dtype: leave kv_dtype out)")
         sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, generator=generator)
         out = _continue(model, input_ids, max_new_tokens, cache, lengths, sampling, eos_token_id, pad_token_id,
                         graph, sync_every)

@@ -39,8 +39,9 @@ append_attention (K17) a block of new tokens over a KV cache (multi-turn  append
                        continuation): RoPE + cache append at per-       fwd_kernel's body over the
                        sequence offsets + causal attention over the      cache; attn_common.h;
                        cache; device-side start / nnew; head dim 64 |    split keys + merge kernel
-                       128; long histories split over keys               on a host-side plan,
-                                                                         append_key_splits)
+                       128; long histories split over keys; bf16 or      on a host-side plan,
+                       fp8 (e4m3, ``q8`` rows) cache, dequantised        append_key_splits; <.., F8>
+                       while a tile is staged into LDS                   kernels, kv8.h)
 =====================  ==============================================  =========================
 
 GPU tensors always go to the HIP kernels; if ``libnbd_ops.so`` cannot be loaded on a GPU box the

@@ -7,8 +7,9 @@ step streams); qkv and the output stay bf16.
 Shared prefix (``decode_attention_shared``): ``group`` consecutive sequences read one prompt's prefix
 rows and then their own — several samples per prompt with the prompt held once.
 Block append (K17, ``csrc/kernels/append.hip``): several new tokens per sequence at per-sequence
-offsets — what continuing from a returned cache runs instead of a second prefill (bf16 cache,
-head dim 64 or 128).
+offsets — what continuing from a returned cache runs instead of a second prefill (bf16 or fp8
+cache, head dim 64 or 128).  An fp8 cache holds :func:`q8` rows here too: the new rows are stored
+quantised, and a new token attends over the cache as stored, its own row included.
 """
 from __future__ import annotations
 
@@ -231,11 +232,16 @@ def decode_attention_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, pos, gr
 APPEND_HEAD_DIMS = (64, 128)  # the head dims append.hip is instantiated for
 
 
-def append_supported(qkv, k_cache, n_head: int) -> bool:
+def append_supported(qkv, k_cache, n_head: int, v_cache=None) -> bool:
+    """Whether ``append.hip`` takes this call.  With ``k_cache`` alone the answer is the one for a bf16
+    pair; fp8 caches are taken when both are seen to be ``float8_e4m3fn`` (the kernel has no mixed
+    variant), so pass ``v_cache`` to ask about them."""
     import torch
 
     Hkv = k_cache.shape[1]
-    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16
+    dtypes = (torch.bfloat16,) if v_cache is None else (torch.bfloat16, torch.float8_e4m3fn)
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and k_cache.dtype in dtypes
+            and (v_cache is None or v_cache.dtype == k_cache.dtype)
             and k_cache.shape[-1] in APPEND_HEAD_DIMS and n_head % Hkv == 0)
 
 
@@ -250,7 +256,9 @@ def _append_span(start, nnew, Tn: int, limit: int):
 
 def append_attention_reference(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Optional[float] = None,
                                rope=None, kv_len_max: Optional[int] = None):
-    """PyTorch version of :func:`append_attention` (fp32 math, writes the caches the same way)."""
+    """PyTorch version of :func:`append_attention` (fp32 math, writes the caches the same way: on
+    fp8 caches the new rows are stored as :func:`q8` makes them — of the bf16-rounded row — and the
+    block attends over the caches as stored)."""
     import torch
 
     B, Tn, W = qkv.shape
@@ -275,8 +283,8 @@ def append_attention_reference(qkv, k_cache, v_cache, start, nnew, n_head: int, 
 
         q, k = rot(q), rot(k)
     bi, ti = valid.nonzero(as_tuple=True)
-    k_cache[bi, :, pos[bi, ti]] = k[bi, ti].to(k_cache.dtype)
-    v_cache[bi, :, pos[bi, ti]] = v[bi, ti].to(v_cache.dtype)
+    k_cache[bi, :, pos[bi, ti]] = _to_cache(k[bi, ti], k_cache.dtype)
+    v_cache[bi, :, pos[bi, ti]] = _to_cache(v[bi, ti], v_cache.dtype)
     # rows >= start + nnew hold nothing of this sequence (possibly NaN): zeros, and masked below
     t = torch.arange(Tmax, device=dev)
     held = (t[None, :] < (start + nnew)[:, None])[:, None, :, None]  # [B, 1, Tmax, 1]
@@ -325,19 +333,26 @@ def append_attention(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Opt
     (1 ≤ nnew[b] ≤ Tn; rows past it are padding).  For i < nnew[b] the new k (rotated at position
     start[b] + i when ``rope`` = (cos, sin) tables) and v are written to cache row start[b] + i and
     query i attends rows 0..start[b] + i; no later row influences it, whatever it holds, and rows
-    ≥ start[b] + nnew[b] are not written.  ``kv_len_max`` is a host bound on max(start + nnew)
+    ≥ start[b] + nnew[b] are not written.  The caches are bf16 or both ``float8_e4m3fn``: an fp8
+    cache holds :func:`q8` rows (the bf16 row clamped to ±448 and rounded to nearest even, no
+    scales), the new rows are stored that way, and a new token attends over its own row as stored
+    — the result is what the bf16 kernel gives on a bf16 cache holding the dequantised rows.
+    ``kv_len_max`` is a host bound on max(start + nnew)
     (default Tmax).  ``key_splits``: 0 = the kernel's plan splits the sweep over keys into chunks
     when that fills the chip (:func:`append_key_splits`), 1 = never, n > 1 = n chunks whatever the
     plan says; ``None`` = ``APPEND_KEY_SPLITS`` (``NBD_APPEND_SPLIT``: ``auto`` | ``0`` never | n); the
-    PyTorch path ignores it.  Returns [B, Tn, H·D] with exact zeros on the padding rows.  GPU bf16 (qkv and
-    caches), head dim 64 or 128 (the caches' last dim; ``rope`` tables [≥ Tmax, D/2]) →
+    PyTorch path ignores it.  Returns [B, Tn, H·D] with exact zeros on the padding rows.  GPU, bf16 qkv,
+    bf16 or fp8 caches, head dim 64 or 128 (the caches' last dim; ``rope`` tables [≥ Tmax, D/2]) →
     ``csrc/kernels/append.hip``; elsewhere — CPU, other dtypes, other head dims — the same math in
     PyTorch (:func:`append_attention_reference`)."""
     import torch
 
     D = k_cache.shape[-1]
     sc = float(scale) if scale is not None else D ** -0.5
-    if append_supported(qkv, k_cache, n_head):
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"append_attention: k_cache ({k_cache.dtype}) and v_cache ({v_cache.dtype}) must have "
+                         f"the same dtype")
+    if append_supported(qkv, k_cache, n_head, v_cache):
         _require()
         Tmax = k_cache.shape[2]
         cos, sin = rope if rope is not None else (None, None)
