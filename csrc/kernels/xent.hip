@@ -21,6 +21,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <cmath>
 #include <tuple>
 
@@ -42,6 +43,8 @@ struct OnlineLse {
       m = t;
     } else if (m != -INFINITY) {
       s += __builtin_amdgcn_exp2f(t - m);
+    } else if (t != t) {
+      s = t;  // a NaN before any finite element: neither compare above sees it, the sum must
     }
   }
   __device__ __forceinline__ void add8(const float (&v)[8]) {
@@ -52,7 +55,13 @@ struct OnlineLse {
       t[j] = v[j] * kLog2e;
       cm = fmaxf(cm, t[j]);
     }
-    if (cm == -INFINITY) return;  // all masked
+    if (cm == -INFINITY) {  // all masked, or NaNs that fmaxf skipped: -inf + ... + -inf is NaN only then
+      float a = t[0];
+#pragma unroll
+      for (int j = 1; j < 8; ++j) a += t[j];
+      if (a != a) s = a;
+      return;
+    }
     if (cm > m) {
       s *= __builtin_amdgcn_exp2f(m - cm);
       m = cm;
@@ -62,7 +71,10 @@ struct OnlineLse {
   }
   __device__ __forceinline__ void merge(float m2, float s2) {
     const float M = fmaxf(m, m2);
-    if (M == -INFINITY) return;
+    if (M == -INFINITY) {  // nothing finite on either side: only a NaN to carry (0 + 0 otherwise)
+      s += s2;
+      return;
+    }
     s = s * __builtin_amdgcn_exp2f(m - M) + s2 * __builtin_amdgcn_exp2f(m2 - M);
     m = M;
   }
@@ -384,6 +396,19 @@ std::tuple<at::Tensor, at::Tensor> xent_fused_hip(const at::Tensor& logits, cons
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(logits.device());
   hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
   const int64_t ld = logits.stride(0);
+  // a row's chunk count depends on its 16-B phase: (V - head) / 8 with a head of 0..7 elements, and
+  // the largest instance holds 256·32 chunks — past 65,536 + 7 columns a row fits only if it starts
+  // late enough before a boundary (65,536 + 14: head 7, tail 7).  The rows' phases repeat with a
+  // period of at most 8 rows; a chunk beyond the instance would silently stay out of the loss.
+  int64_t max_nv = 0;
+  for (int64_t r = 0; r < std::min<int64_t>(N, 8); ++r) {
+    const uintptr_t p = (uintptr_t)logits.data_ptr() + (uintptr_t)(r * ld * 2);
+    const int64_t head = std::min<int64_t>((int64_t)(((16u - (p & 15u)) & 15u) / 2), V);
+    max_nv = std::max<int64_t>(max_nv, (V - head) / 8);
+  }
+  TORCH_CHECK(max_nv <= (int64_t)kXentThreads * kFusedChunks,
+              "xent_fused: vocabulary too large for the rows' 16-byte alignment (", max_nv, " chunks of 8 in a row, at most ",
+              kXentThreads * kFusedChunks, ")");
   // registers per lane scale with the chunk count: use the smallest instance covering the row
   const int64_t need = (V + (int64_t)kXentThreads * 8 - 1) / ((int64_t)kXentThreads * 8);
   const bool bf = logits.scalar_type() == at::kBFloat16;

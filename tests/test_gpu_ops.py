@@ -1,4 +1,5 @@
-"""GPU numerics: the HIP kernels (torch.ops.nbd.*) against plain PyTorch fp32 references."""
+"""GPU numerics: the HIP kernels (torch.ops.nbd.*) against plain PyTorch fp32 references.
+The numerical authority for xent.hip is tests/test_gpu_xent_paths.py (fp64 reference, per element)."""
 import math
 
 import pytest

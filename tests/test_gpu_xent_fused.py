@@ -1,7 +1,8 @@
 """GPU numerics: the one-pass LM-head loss (``nbd::xent_fused`` in csrc/kernels/xent.hip and
 ``ops.linear_cross_entropy``) against a plain fp32 PyTorch reference of the same bf16 inputs —
 loss, and dh / dW through autograd; every register-chunk instance (8, 16, 25, 32), odd vocabularies
-(unaligned rows: scalar head and tail lanes), ignore_index rows, sum reduction, grad_out ≠ 1."""
+(unaligned rows: scalar head and tail lanes), ignore_index rows, sum reduction, grad_out ≠ 1.
+The numerical authority for xent.hip is tests/test_gpu_xent_paths.py (fp64 reference, per element)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -167,7 +168,7 @@ def test_linear_cross_entropy_mixed_products(dev, products, monkeypatch):
     assert len(calls) == sum(not v for v in products.values())
 
 
-@pytest.mark.parametrize("n", [1, 96, 8192, 70001])
+@pytest.mark.parametrize("n", [1, 96, 1023, 1024, 1025, 8192, 70001])  # 1024: one stride of the thread loop
 def test_loss_scalar_ops(dev, n):
     """xent_mean_scale / xent_loss_total (the mean reduction's two one-launch scalars) and
     scale_pair_ (the backward's dh *= g, h·g) against fp32 PyTorch."""
@@ -188,6 +189,22 @@ def test_loss_scalar_ops(dev, n):
     a_ref, b_ref = (a.float() * 0.37).to(torch.bfloat16), (b.float() * 0.37).to(torch.bfloat16)
     out = torch.ops.nbd.scale_pair_(a, b, g)
     assert torch.equal(a, a_ref) and torch.equal(out, b_ref)
+    # a large common mean and a small spread: the sum against fp64 at an fp32 bound — each value
+    # passes through at most ceil(n / 1024) + 6 + 16 additions (thread loop, wave shuffles, the 16
+    # waves) and the product with the scale, every one within 2^-24 of the running magnitude
+    rows = 1000.0 + 1e-3 * torch.randn(n, device=dev)
+    one = torch.ones(1, device=dev)
+    tot = torch.ops.nbd.xent_loss_total(rows, s if valid else one)
+    sv = float(s) if valid else 1.0
+    ref = float(rows.double().sum()) * sv
+    depth = -(-n // 1024) + 6 + 16 + 1
+    assert abs(float(tot) - ref) <= depth * 2.0 ** -24 * float(rows.double().abs().sum()) * sv, (float(tot), ref)
+    # scale_pair_ on fp16
+    a = torch.randn(n * 8, device=dev).to(torch.float16)
+    b = torch.randn(n * 8, device=dev).to(torch.float16)
+    a_ref, b_ref = (a.float() * g).to(torch.float16), (b.float() * g).to(torch.float16)
+    out = torch.ops.nbd.scale_pair_(a, b, g)
+    assert out.dtype == torch.float16 and torch.equal(a, a_ref) and torch.equal(out, b_ref)
 
 
 def test_mean_scale_all_ignored(dev):
