@@ -61,6 +61,14 @@ points; cache bytes derived from the shapes.
 
     python benchmarks/generate_bench.py --continue --kv-dtype fp8 [--head-dim 128] [--layers 4] [--batches 1,8]
         [--hist 512,2048,4096] [--turn 1,32,128] [--rounds 7] [--out table.json]
+
+``--shared R --continue``: the first token of turn 2 from the shared-prefix cache (B prompts x R samples,
+``ops.append_attention_shared``) against materialising the B·R private caches and continuing those,
+and against re-prefilling the repeated history; ``ops.append_attention_shared`` alone against
+``ops.append_attention`` on the materialised cache.  SmolLM2-135M and the head-dim-128 stack.
+
+    python benchmarks/generate_bench.py --shared 8 --continue [--batches 4] [--prompts 2048] [--layers 4]
+        [--turn 1,32,128] [--rounds 7] [--out table.json]
 """
 from __future__ import annotations
 
@@ -800,6 +808,109 @@ def kv8_continue_bench(a):
             json.dump(res, f, indent=1)
 
 
+def shared_continue_bench(a):
+    """``--shared R --continue``: the first token of turn 2 from the shared-prefix cache of B prompts x R
+    samples (``ops.append_attention_shared``) against what there was without it — materialise the
+    B·R private caches from the shared one and continue those, or re-prefill the repeated history —
+    and ``ops.append_attention_shared`` alone against ``ops.append_attention`` on the materialised
+    cache.  SmolLM2-135M and the Llama-3.2-3B-shaped stack of ``--layers`` layers; rounds interleaved,
+    medians.  No ratio is a target: a point where the shared arm is slower is reported as it comes out."""
+    import statistics
+
+    from nbdistributed_amd import ops
+    from nbdistributed_amd.generation import KVCache, generate
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+
+    R, B, P, NEW1 = a.shared, int(a.batches.split(",")[0]), int(a.prompts.split(",")[-1]), 8
+    turns = [int(x) for x in a.turn.split(",")]
+    med = lambda xs: round(statistics.median(xs), 3)  # noqa: E731
+    res = {"what": f"turn 2 from a shared-prefix cache: {B} prompts of {P} tokens x {R} samples, {NEW1} tokens of turn 1; "
+                   f"points = ms to the first token of turn 2 (eager), kernel = us per op call; medians of interleaved rounds",
+           "rounds": a.rounds, "points": [], "kernel": []}
+
+    def materialise(sh):
+        c = KVCache(sh.n_layer, sh.batch, sh.n_head, sh.n_kv, sh.t_max, sh.head_dim, dtype=sh.k.dtype, device=sh.k.device)
+        for full, pre, own in ((c.k, sh.k, sh.k_own), (c.v, sh.v, sh.v_own)):
+            full[:, :, :, :P] = pre[:, :, :, :P].repeat_interleave(R, 1)
+            full[:, :, :, P:P + sh.t_own] = own
+        return c
+
+    for name in ("smollm2", "llama3b-shaped"):
+        torch.manual_seed(0)
+        if name == "smollm2":
+            m, vocab, _, (H, Hkv) = _bench_model(name, P + 256)
+        else:
+            vocab, H, Hkv = 32000, 24, 8
+            m = LlamaForCausalLM(LlamaConfig(vocab_size=vocab, hidden_size=3072, intermediate_size=8192,
+                                             num_hidden_layers=a.layers, num_attention_heads=H, num_key_value_heads=Hkv,
+                                             max_position_embeddings=8192, explicit_head_dim=128)).to("cuda", torch.bfloat16).eval()
+        D = m.kv_layout()[3]
+        ids = torch.randint(1, vocab, (B, P), device="cuda")
+        t_max = P + NEW1 + max(turns) + 8
+        out1, sh = generate(m, ids, NEW1, temperature=1.0, num_return_sequences=R, t_max=t_max, graph=False,
+                            return_cache=True)
+        state = (sh.lengths.clone(), sh.pending.clone())
+        for turn in turns:
+            new = torch.randint(1, vocab, (B * R, turn), device="cuda")
+
+            def cont(c):
+                c.lengths, c.pending = state[0].clone(), state[1].clone()
+                return generate(m, new, 1, cache=c, graph=False)
+
+            arms = {"shared": lambda: cont(sh), "materialise_and_continue": lambda: cont(materialise(sh)),
+                    "reprefill": lambda: generate(m, torch.cat([out1, new], 1), 1, graph=False)}
+            first = {k: f()[:, -1] for k, f in arms.items()}  # (also the warm-up of every arm)
+            ms = {k: [] for k in arms}
+            for _ in range(a.rounds):
+                for k, f in arms.items():
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    f()
+                    torch.cuda.synchronize()
+                    ms[k].append((time.perf_counter() - t) * 1e3)
+            row = dict(model=name, head_dim=D, turn=turn, **{k: med(v) for k, v in ms.items()},
+                       **{k + "_min_max": [round(min(v), 3), round(max(v), 3)] for k, v in ms.items()},
+                       cache_bytes={"shared": sh.nbytes, "materialised": materialise(sh).nbytes},
+                       first_token_same_as_materialised=bool((first["shared"] == first["materialise_and_continue"]).all()))
+            print(json.dumps(row), flush=True)
+            res["points"].append(row)
+            # the op alone, at this model's heads: the shared caches against the materialised one
+            Tn, S, To = turn + 1, B * R, sh.t_own
+            rnd = lambda *s: torch.randn(*s, device="cuda").to(torch.bfloat16)  # noqa: E731
+            qkv, kp, vp, ko, vo = rnd(S, Tn, (H + 2 * Hkv) * D), rnd(B, Hkv, P, D), rnd(B, Hkv, P, D), rnd(S, Hkv, To, D), rnd(S, Hkv, To, D)
+            kf, vf = (torch.cat([p_.repeat_interleave(R, 0), o_], 2) for p_, o_ in ((kp, ko), (vp, vo)))
+            pl = torch.full((B,), P, device="cuda", dtype=torch.int64)
+            st = torch.full((S,), P + NEW1 - 1, device="cuda", dtype=torch.int64)
+            nn = torch.full((S,), Tn, device="cuda", dtype=torch.int64)
+            rope, bound = ops.rope_tables(P + To, D, 10000.0, "cuda"), P + NEW1 - 1 + Tn
+            calls = {"shared": lambda: ops.append_attention_shared(qkv, kp, vp, pl, ko, vo, st, nn, R, H, rope=rope, kv_len_max=bound),
+                     "materialised": lambda: ops.append_attention(qkv, kf, vf, st, nn, H, rope=rope, kv_len_max=bound)}
+            for f in calls.values():
+                for _ in range(3):
+                    f()
+            torch.cuda.synchronize()
+            us, n = {k: [] for k in calls}, 20
+            for _ in range(a.rounds):
+                for k, f in calls.items():
+                    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    s.record()
+                    for _ in range(n):
+                        f()
+                    e.record()
+                    e.synchronize()
+                    us[k].append(s.elapsed_time(e) / n * 1e3)
+            row = dict(model=name, head_dim=D, S=S, H=H, Hkv=Hkv, prefix=P, Tn=Tn, **{k: med(v) for k, v in us.items()},
+                       key_splits=ops.append_key_splits(S, H, Tn, bound, D),
+                       cache_rows_bytes={"shared": 4 * Hkv * D * (B * P + S * To), "materialised": 4 * Hkv * D * S * (P + To)})
+            print(json.dumps(row), flush=True)
+            res["kernel"].append(row)
+        del m, sh
+        torch.cuda.empty_cache()
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--head-dim", dest="head_dim", type=int, default=0, choices=[0, 128],
@@ -832,6 +943,10 @@ def main():
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.shared and a.cont:
+        if a.batches == "1,8,32":
+            a.batches = "4"
+        return shared_continue_bench(a)
     if a.kv_dtype and a.cont:
         if a.batches == "1,8,32":
             a.batches = "1,8"

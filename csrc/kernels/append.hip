@@ -96,6 +96,51 @@
 //     (the launch bounds are the bf16 kernels'); append_kv <64 | 128, true> 50 VGPR (bf16: 49).
 //     No packed fp32 instruction in the unit, with -fno-slp-vectorize as it is built.
 //
+// Shared prefix (append_kv_kernel<D, F8, true>, append_attn_kernel<D, SPLIT, F8, true>,
+// append_merge_kernel<D, true>; op append_attn_shared; the cache of several samples per prompt,
+// decode.hip's decode_kernel<.., SHARED>): sequence s of S = B · group continues prompt p = s / group.
+// Position j of it lives in prefix[p, kvh, j] for j < plen[p] and in own[s, kvh, j - plen[p]] from
+// there on; plen is int64 [B] on the device, start stays an absolute position, nothing synchronises,
+// and grids and workspace follow host values only (S, H, Tn, kv_len_max, D) as above.
+//   * clamps, before anything is addressed: plen into [0, Tp], start - plen into [0, To - 1], nnew
+//     into [0, min(Tn, To - (start - plen), L - start)] (span_of's second form; the merge kernel
+//     takes the same one, so it reads the slots the attention kernel wrote under it).
+//   * append_kv_kernel: the block's row at position start + i, rotated there, becomes own row
+//     start + i - plen.  The prefix is never written.
+//   * append_attn_kernel: only where a staged row comes from changes.  The own base of the
+//     (sequence, kv head) is set back by plen rows, so the absolute key index addresses prefix and
+//     own rows alike and the row clamp is one bound, plen + To - 1.  A 64-key tile is then one of
+//     three cases, decided by scalar compares of the tile index with plen (uniform in the
+//     workgroup): wholly prefix or wholly own — one base pointer, the unshared loads (RowsOne) —
+//     or the one tile per sequence that holds key plen when plen is no multiple of 64, which
+//     selects the base per row (RowsTwo: a compare and two v_cndmask per base; the row index is
+//     the same either way).  load_tile branches between the two forms; both leave their loads in
+//     flight, so the next tile streams under the current tile's math across the prefix-to-own
+//     boundary as anywhere else.  Zeros on the row index come after the select: prefix rows
+//     >= plen are never addressed (own rows stand there), own rows >= start - plen + nnew are keys
+//     >= kend.  LDS images, transposed reads, MFMA body, softmax, diagonal, sweep bounds, chunk
+//     edges and partials are the unshared kernel's: the output equals, bit for bit, the unshared
+//     kernel's on the materialised cache (tests/test_gpu_append_shared.py), bf16 and fp8, split
+//     and unsplit.
+//   * grid order is the unshared one — batch · head fastest within a (query block, chunk) — so the
+//     workgroups of the `group` samples of a prompt are neighbours in the grid and their prefix
+//     tiles can meet in L2 / MALL instead of streaming `group` copies from HBM.  A design intent:
+//     the residency was not measured (docs/FINDINGS.md §50 has the times).
+//   * the parameters are a type of their own (SharedAppendParams, AppendParams plus five fields), so
+//     the unshared kernels keep their kernarg segment.  Their ISA against the previous build: the
+//     128 unsplit attention kernels, append_kv and merge are instruction for instruction what they
+//     were; the 128 split kernels differ in the operand order of one v_add_f32; the 64 attention
+//     kernels hold the same instructions, with the v_cndmask that zero a staged tile (and their
+//     registers) in another order.  The compiler's choice — the loads moved into a lambda over the
+//     row source — and not a change of work.
+//   * the new instantiations, VGPR / AGPR / scratch / waves per SIMD / LDS (<D, SPLIT, F8, true>):
+//     <64, false, false> 171 / 0 / 0 / 2 / 21 504, <64, true, false> 173 / 0 / 0 / 2 / 21 504,
+//     <64, false, true> 163 / 0 / 0 / 3 / 21 504, <64, true, true> 171 / 0 / 0 / 2 / 21 504,
+//     <128, false, false> 256 / 135 / 0 / 1 / 37 888, <128, true, false> 256 / 135 / 0 / 1 / 37 888,
+//     <128, false, true> 256 / 129 / 0 / 1 / 37 888, <128, true, true> 253 / 128 / 0 / 1 / 37 888:
+//     no scratch anywhere, the launch bounds are the unshared kernels'.  The four bases and plen
+//     are scalar registers.
+//
 // Head dim: both kernels take it as a template parameter, D = 64 | 128 (the host reads it from the
 // caches' last dim); "64" above stands for D.  The algorithm is the same; what follows D:
 //   * a lane holds D/16 query fragments, S takes D/16 MFMA k-steps per 32-key block, O is D/32
@@ -166,6 +211,31 @@ __device__ __forceinline__ Span span_of(const AppendParams& p, int b) {
   return s;
 }
 
+// the <.., SHARED = true> kernels (header: shared prefix): kc / vc are the sequences' own rows
+// [B, Hkv, To, D], sequence b reads rows [0, plen[b / group]) of prompt b / group's prefix before
+// them; Tmax = Tp + To and L count absolute positions.  A type of its own, so the unshared kernels'
+// kernarg segment is what it was.
+struct SharedAppendParams : AppendParams {
+  const uint16_t* kp;   // [B / group, Hkv, Tp, D] contiguous, the dtype of kc / vc; never written
+  const uint16_t* vp;
+  const int64_t* plen;  // [B / group]
+  int group, Tp, To;
+};
+template <bool SHARED>
+using ParamsOf = std::conditional_t<SHARED, SharedAppendParams, AppendParams>;
+
+// the same behind a prefix: plen into [0, Tp], start - plen into [0, To - 1] (the block never lands
+// in the prefix), nnew into [0, min(Tn, To - (start - plen), L - start)].  s0 stays absolute; the
+// rows of the block are own rows s0 - pl .. s0 - pl + n - 1 <= To - 1.
+__device__ __forceinline__ Span span_of(const SharedAppendParams& p, int b, int& pl) {
+  pl = (int)min<int64_t>(max<int64_t>(p.plen[b / p.group], 0), p.Tp);
+  const int o0 = (int)min<int64_t>(max<int64_t>(p.start[b] - pl, 0), p.To - 1);
+  Span s;
+  s.s0 = pl + o0;
+  s.n = (int)max<int64_t>(min<int64_t>(max<int64_t>(p.nnew[b], 0), min(min(p.Tn, p.To - o0), p.L - s.s0)), 0);
+  return s;
+}
+
 __device__ __forceinline__ s8v zero8() {
   s8v z;
 #pragma unroll
@@ -202,13 +272,36 @@ struct StageRows8 {
   }
 };
 
+// where the rows of a staged tile come from: at<0>(r) / at<1>(r) is the k / v base that key row r
+// is addressed from, rows the row indices that may be addressed (clamped to rows - 1).  RowsOne: one run of rows — an
+// unshared cache, or a tile of a shared one that lies wholly in the prefix or wholly in own rows.
+// RowsTwo: the tile that straddles plen selects per row (two v_cndmask per base).
+struct RowsOne {
+  const uint16_t* base[2];
+  int rows;
+  template <int V>
+  __device__ __forceinline__ const uint16_t* at(int) const {
+    return base[V];
+  }
+};
+struct RowsTwo {
+  const uint16_t* pre[2];
+  const uint16_t* own[2];  // set back by plen rows: indexed by the absolute key row
+  int pl, rows;
+  template <int V>
+  __device__ __forceinline__ const uint16_t* at(int r) const {
+    return r < pl ? pre[V] : own[V];
+  }
+};
+
 // ============================================================================ cache append
 // thread = (b, i, kv head, c), c < D/16: dims [8c, 8c + 8) and their rotation partners
 // [D/2 + 8c, D/2 + 8c + 8) of k, the same two 16-B chunks of v.  F8: each chunk is stored as its 8
 // e4m3 bytes, q8 of the bf16 chunk — the rotated k is rounded fp32 -> bf16 -> e4m3, like a
-// prefilled row and like decode.hip's
-template <int D, bool F8>
-__global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t total) {
+// prefilled row and like decode.hip's.  SHARED: position t is own row t - plen; the prefix is not
+// written
+template <int D, bool F8, bool SHARED>
+__global__ __launch_bounds__(NT) void append_kv_kernel(ParamsOf<SHARED> p, int64_t total) {
   static_assert(D == 64 || D == 128, "head dim 64 or 128");
   constexpr int HALF = D / 2;
   const int64_t g = (int64_t)blockIdx.x * NT + threadIdx.x;
@@ -218,7 +311,14 @@ __global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t t
   const int kvh = (int)(rowi % p.Hkv);
   const int i = (int)(rowi / p.Hkv % p.Tn);
   const int b = (int)(rowi / p.Hkv / p.Tn);
-  const Span sp = span_of(p, b);
+  Span sp;
+  int tmax = p.Tmax, off = 0;  // rows per (sequence, kv head) of kc / vc; the position of their row 0
+  if constexpr (SHARED) {
+    sp = span_of(p, b, off);
+    tmax = p.To;
+  } else {
+    sp = span_of(p, b);
+  }
   if (i >= sp.n) return;  // padding: nothing lands in the cache
   const int t = sp.s0 + i;
   const uint16_t* row = p.qkv + b * p.sb + i * p.st;
@@ -226,7 +326,7 @@ __global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t t
   const uint16_t* vs = row + (p.H + p.Hkv + kvh) * D + c * 8;
   s8v ka = ld16(ks), kb = ld16(ks + HALF);
   if (p.rp.cos != nullptr) rope8_hd<HALF>(ka, kb, p.rp, t, c * 8);
-  const int64_t dst = (((int64_t)b * p.Hkv + kvh) * p.Tmax + t) * D + c * 8;
+  const int64_t dst = (((int64_t)b * p.Hkv + kvh) * tmax + (t - off)) * D + c * 8;
   if constexpr (F8) {  // dst counts elements: bytes here
     uint8_t* const k8 = reinterpret_cast<uint8_t*>(p.kc) + dst;
     uint8_t* const v8 = reinterpret_cast<uint8_t*>(p.vc) + dst;
@@ -248,8 +348,10 @@ __global__ __launch_bounds__(NT) void append_kv_kernel(AppendParams p, int64_t t
 // built for one wave per SIMD, where it spills nothing.
 // SPLIT: a workgroup sweeps one chunk of its query block's tiles and stores fp32 partials (header)
 // F8: the caches hold e4m3 bytes; only load_tile and the staging structs differ (header)
-template <int D, bool SPLIT, bool F8>
-__global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(AppendParams p) {
+// SHARED: keys below plen come from the prompt's prefix, the rest from own rows; only where
+// load_tile takes a row from differs (header)
+template <int D, bool SPLIT, bool F8, bool SHARED>
+__global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(ParamsOf<SHARED> p) {
   static_assert(D == 64 || D == 128, "head dim 64 or 128");
   constexpr int RS = D + 8;                // K image row stride (elements): row reads
   constexpr int RSV = D == 64 ? 96 : 160;  // V image row stride: transposed reads (header: banks)
@@ -272,7 +374,12 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
   const int b = bh / p.H, hh = bh % p.H;
   const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, h = lane >> 5;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const Span sp = span_of(p, b);
+  Span sp;
+  int pl = 0;  // SHARED: the prompt's prefix rows, uniform in the workgroup
+  if constexpr (SHARED)
+    sp = span_of(p, b, pl);
+  else
+    sp = span_of(p, b);
   const int s0 = sp.s0, n = sp.n;
   const int nl = max(n - 1, 0);        // the last valid query
   const int kend = s0 + n;             // cache rows >= kend hold nothing of this sequence
@@ -304,50 +411,59 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
   float m = -INFINITY, l = 0.f;
 
   // (F8: a row is D bytes, so the head's first row sits at half this element offset)
-  const int64_t hoff = ((int64_t)b * p.Hkv + kh) * p.Tmax * (F8 ? D / 2 : D);
+  constexpr int RE = F8 ? D / 2 : D;  // a cache row in elements of the base pointers
+  int crows = p.Tmax;  // rows per (sequence, kv head) of kc / vc
+  if constexpr (SHARED) crows = p.To;
+  const int64_t hoff = ((int64_t)b * p.Hkv + kh) * crows * RE;
   const uint16_t* kbase = p.kc + hoff;
   const uint16_t* vbase = p.vc + hoff;
   // the 64 tile keeps the fixed staging structs, so that instantiation stays the kernel it was
   std::conditional_t<F8, std::conditional_t<D == 64, StagePair8, StageRows8<D>>,
                      std::conditional_t<D == 64, StagePair, StageRows<D>>> sk;
   std::conditional_t<F8, StageRows8<D>, std::conditional_t<D == 64, Stage2, StageRows<D>>> sv;
-  // a tile's rows from the cache (row index clamped into it); rows >= kend become zeros
-  auto load_rows = [&](StageRows<D>& sr, const uint16_t* base, int k0) {  // (128)
+  // a tile's rows from `src` (RowsOne | RowsTwo: the base of key row r and the count of rows that
+  // may be addressed; the row index clamped below it); rows >= kend become zeros
+  auto load_rows = [&](StageRows<D>& sr, auto v_c, const auto& src, int k0) {  // (128)
+    constexpr int V = decltype(v_c)::value;
 #pragma unroll
     for (int i = 0; i < D / 32; ++i) {
       const int c = tid + i * NT;
       const int vr = k0 + (c >> (D == 64 ? 3 : 4));
-      sr.a[i] = ld16(base + (int64_t)min(vr, p.Tmax - 1) * D + (c & (D / 8 - 1)) * 8);
+      sr.a[i] = ld16(src.template at<V>(vr) + (int64_t)min(vr, src.rows - 1) * D + (c & (D / 8 - 1)) * 8);
       if (vr >= kend) sr.a[i] = zero8();
     }
   };
   // F8: the same rows as 8-B pieces, one per ld16 of the bf16 tile; the row index decides on the
   // zeros before anything is converted, so a NaN byte of a free row never reaches LDS
-  auto load_rows8 = [&](StageRows8<D>& sr, const uint16_t* base, int k0) {
-    const uint8_t* const base8 = reinterpret_cast<const uint8_t*>(base);
+  auto load_rows8 = [&](StageRows8<D>& sr, auto v_c, const auto& src, int k0) {
+    constexpr int V = decltype(v_c)::value;
 #pragma unroll
     for (int i = 0; i < D / 32; ++i) {
       const int c = tid + i * NT;
       const int vr = k0 + (c >> (D == 64 ? 3 : 4));
-      sr.a[i] = ld8(base8 + (int64_t)min(vr, p.Tmax - 1) * D + (c & (D / 8 - 1)) * 8);
+      const uint8_t* const base8 = reinterpret_cast<const uint8_t*>(src.template at<V>(vr));
+      sr.a[i] = ld8(base8 + (int64_t)min(vr, src.rows - 1) * D + (c & (D / 8 - 1)) * 8);
       if (vr >= kend) sr.a[i] = u32x2{0u, 0u};
     }
   };
-  auto load_tile = [&](int k0) {
+  constexpr std::integral_constant<int, 0> K_{};
+  constexpr std::integral_constant<int, 1> V_{};
+  auto load_from = [&](int k0, const auto& src) {
     if constexpr (F8) {
       if constexpr (D == 64) {  // StagePair's mapping: row tid / 4, pieces q and q + 4
         const int kr = k0 + (tid >> 2);
-        const uint8_t* pk = reinterpret_cast<const uint8_t*>(kbase) + (int64_t)min(kr, p.Tmax - 1) * D + (tid & 3) * 8;
+        const uint8_t* pk = reinterpret_cast<const uint8_t*>(src.template at<0>(kr)) + (int64_t)min(kr, src.rows - 1) * D +
+                            (tid & 3) * 8;
         sk.a = ld8(pk);
         sk.b = ld8(pk + 32);
         if (kr >= kend) sk.a = sk.b = u32x2{0u, 0u};
       } else {
-        load_rows8(sk, kbase, k0);
+        load_rows8(sk, K_, src, k0);
       }
-      load_rows8(sv, vbase, k0);
+      load_rows8(sv, V_, src, k0);
     } else if constexpr (D == 64) {
       const int kr = k0 + (tid >> 2);
-      const uint16_t* pk = kbase + (int64_t)min(kr, p.Tmax - 1) * D + (tid & 3) * 8;
+      const uint16_t* pk = src.template at<0>(kr) + (int64_t)min(kr, src.rows - 1) * D + (tid & 3) * 8;
       sk.a = ld16(pk);
       sk.b = ld16(pk + 32);
       if (kr >= kend) sk.a = sk.b = zero8();
@@ -355,12 +471,38 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
       for (int i = 0; i < 2; ++i) {
         const int c = tid + i * NT;
         const int vr = k0 + (c >> 3);
-        sv.a[i] = ld16(vbase + (int64_t)min(vr, p.Tmax - 1) * D + (c & 7) * 8);
+        sv.a[i] = ld16(src.template at<1>(vr) + (int64_t)min(vr, src.rows - 1) * D + (c & 7) * 8);
         if (vr >= kend) sv.a[i] = zero8();
       }
     } else {
-      load_rows(sk, kbase, k0);
-      load_rows(sv, vbase, k0);
+      load_rows(sk, K_, src, k0);
+      load_rows(sv, V_, src, k0);
+    }
+  };
+  // SHARED: the prefix of this (prompt, kv head), and the own rows set back by plen rows, so that
+  // the absolute key index addresses both; own rows end at key plen + To - 1
+  const uint16_t *kpre = nullptr, *vpre = nullptr, *kown = nullptr, *vown = nullptr;
+  if constexpr (SHARED) {
+    const int64_t poff = ((int64_t)(b / p.group) * p.Hkv + kh) * p.Tp * RE;
+    kpre = p.kp + poff;
+    vpre = p.vp + poff;
+    kown = kbase - (int64_t)pl * RE;
+    vown = vbase - (int64_t)pl * RE;
+  }
+  // a tile lies wholly in the prefix or wholly in own rows: one base, chosen by a scalar compare
+  // (uniform in the workgroup).  Only the tile that holds key plen, when plen is no multiple of
+  // 64, picks its base per row.
+  auto load_tile = [&](int k0) {
+    if constexpr (SHARED) {
+      const int rows = pl + p.To;
+      if (k0 < pl && k0 + TILE > pl) {
+        load_from(k0, RowsTwo{{kpre, vpre}, {kown, vown}, pl, rows});
+      } else {
+        const bool pre = k0 < pl;
+        load_from(k0, RowsOne{{pre ? kpre : kown, pre ? vpre : vown}, rows});
+      }
+    } else {
+      load_from(k0, RowsOne{{kbase, vbase}, p.Tmax});
     }
   };
   load_tile(t0 * TILE);
@@ -496,8 +638,9 @@ __global__ __launch_bounds__(NT, D == 64 ? 2 : 1) void append_attn_kernel(Append
 // A query reads the chunks that hold one of its keys, chunk 0 .. lim / (64·chunk_tiles), and no
 // other: those slots were written by this call's append_attn_kernel<D, true> (header).  Fixed
 // order, fp32: bit-reproducible.
-template <int D>
-__global__ __launch_bounds__(NT) void append_merge_kernel(AppendParams p) {
+// SHARED changes the clamp of (start, nnew) only: the one the attention kernel wrote the slots under.
+template <int D, bool SHARED>
+__global__ __launch_bounds__(NT) void append_merge_kernel(ParamsOf<SHARED> p) {
   constexpr int NP = D / 32;  // 8-B pieces of the row per thread
   const int BH = gridDim.x / ((p.Tn + 31) / 32);
   const int bh = blockIdx.x % BH, qt = blockIdx.x / BH;
@@ -505,7 +648,13 @@ __global__ __launch_bounds__(NT) void append_merge_kernel(AppendParams p) {
   const int r = threadIdx.x & 31, g = threadIdx.x >> 5;
   const int qi = qt * 32 + r;
   if (qi >= p.Tn) return;
-  const Span sp = span_of(p, b);
+  Span sp;
+  if constexpr (SHARED) {
+    int pl;
+    sp = span_of(p, b, pl);
+  } else {
+    sp = span_of(p, b);
+  }
   uint16_t* orow = p.out + (((int64_t)b * p.Tn + qi) * p.H + hh) * D;
   if (qi >= sp.n) {  // a padding row: exact zeros
 #pragma unroll
@@ -572,72 +721,107 @@ int64_t append_attn_plan(int64_t batch, int64_t n_head, int64_t Tn, int64_t kv_l
   return plan(batch * n_head * ((Tn + BLK - 1) / BLK), kv_len_max, head_dim, 0).nsplit;
 }
 
-at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                           const at::Tensor& start, const at::Tensor& nnew, int64_t n_head, double scale,
-                           int64_t kv_len_max, const c10::optional<at::Tensor>& rope_cos,
-                           const c10::optional<at::Tensor>& rope_sin, int64_t key_splits) {
+// the operands of append_attn_shared that append_attn has not
+struct Shared {
+  const at::Tensor& k_prefix;
+  const at::Tensor& v_prefix;
+  const at::Tensor& plen;
+  int64_t group;
+};
+
+// both ops: `sh` == nullptr is append_attn (k_cache / v_cache hold every row), else they are the
+// sequences' own rows behind the prompts' prefixes (B counts sequences: prompts · group)
+static at::Tensor append_run(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                             const at::Tensor& start, const at::Tensor& nnew, int64_t n_head, double scale,
+                             int64_t kv_len_max, const c10::optional<at::Tensor>& rope_cos,
+                             const c10::optional<at::Tensor>& rope_sin, int64_t key_splits, const Shared* sh) {
+  const char* op = sh ? "append_attn_shared" : "append_attn";
   TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 && qkv.dim() == 3 && qkv.stride(2) == 1 &&
                   qkv.stride(0) % 8 == 0 && qkv.stride(1) % 8 == 0 && ((uintptr_t)qkv.data_ptr() & 15) == 0,
-              "append_attn: qkv must be a bf16 [B, Tn, (H + 2·Hkv)·D] GPU view, unit last stride, strides multiples "
+              op, ": qkv must be a bf16 [B, Tn, (H + 2·Hkv)·D] GPU view, unit last stride, strides multiples "
               "of 8 elements, 16-B aligned");
   const bool f8 = k_cache.scalar_type() == at::kFloat8_e4m3fn;
-  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(), "append_attn: k_cache (", k_cache.scalar_type(),
+  TORCH_CHECK(k_cache.scalar_type() == v_cache.scalar_type(), op, ": k_cache (", k_cache.scalar_type(),
               ") and v_cache (", v_cache.scalar_type(), ") must have the same dtype, bf16 or float8_e4m3fn");
-  if (f8) {
-    TORCH_CHECK(k_cache.is_cuda() && k_cache.is_contiguous() && k_cache.dim() == 4 && v_cache.dim() == 4 &&
-                    v_cache.is_cuda() && v_cache.is_contiguous() && ((uintptr_t)k_cache.data_ptr() & 7) == 0 &&
-                    ((uintptr_t)v_cache.data_ptr() & 7) == 0,
-                "append_attn: fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, D], 8-B aligned rows");
-  } else {
-    TORCH_CHECK(k_cache.is_cuda() && k_cache.scalar_type() == at::kBFloat16 && k_cache.is_contiguous() &&
-                    k_cache.dim() == 4 && v_cache.dim() == 4 && v_cache.is_cuda() &&
-                    v_cache.scalar_type() == at::kBFloat16 && v_cache.is_contiguous() &&
-                    ((uintptr_t)k_cache.data_ptr() & 15) == 0 && ((uintptr_t)v_cache.data_ptr() & 15) == 0,
-                "append_attn: caches must be contiguous bf16 [B, Hkv, Tmax, D]");
-  }
+  auto check_caches = [&](const at::Tensor& k, const at::Tensor& v) {
+    if (f8) {
+      TORCH_CHECK(k.is_cuda() && k.is_contiguous() && k.dim() == 4 && v.dim() == 4 && v.is_cuda() &&
+                      v.is_contiguous() && k.scalar_type() == at::kFloat8_e4m3fn &&
+                      v.scalar_type() == at::kFloat8_e4m3fn && ((uintptr_t)k.data_ptr() & 7) == 0 &&
+                      ((uintptr_t)v.data_ptr() & 7) == 0,
+                  op, ": fp8 caches must be contiguous float8_e4m3fn [B, Hkv, Tmax, D], 8-B aligned rows");
+    } else {
+      TORCH_CHECK(k.is_cuda() && k.scalar_type() == at::kBFloat16 && k.is_contiguous() && k.dim() == 4 &&
+                      v.dim() == 4 && v.is_cuda() && v.scalar_type() == at::kBFloat16 && v.is_contiguous() &&
+                      ((uintptr_t)k.data_ptr() & 15) == 0 && ((uintptr_t)v.data_ptr() & 15) == 0,
+                  op, ": caches must be contiguous bf16 [B, Hkv, Tmax, D]");
+    }
+  };
+  check_caches(k_cache, v_cache);
   const int64_t D = k_cache.size(3);  // (hides attn::D: the head dim of this call)
-  TORCH_CHECK(D == 64 || D == 128, "append_attn: head dim must be 64 or 128, got ", D, " (the caches' last dim)");
-  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), "append_attn: k_cache ", k_cache.sizes(), " and v_cache ",
+  TORCH_CHECK(D == 64 || D == 128, op, ": head dim must be 64 or 128, got ", D, " (the caches' last dim)");
+  TORCH_CHECK(v_cache.sizes() == k_cache.sizes(), op, ": k_cache ", k_cache.sizes(), " and v_cache ",
               v_cache.sizes(), " must have the same shape (head dim ", D, ")");
-  const int64_t B = qkv.size(0), Tn = qkv.size(1), Hkv = k_cache.size(1), Tmax = k_cache.size(2), H = n_head;
-  TORCH_CHECK(B >= 1 && Tn >= 1 && Tmax >= 1, "append_attn: empty input");
-  TORCH_CHECK(k_cache.size(0) == B, "append_attn: cache batch ", k_cache.size(0), " != ", B);
-  TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0, "append_attn: need H % Hkv == 0");
-  TORCH_CHECK(qkv.size(2) == (H + 2 * Hkv) * D, "append_attn: qkv width ", qkv.size(2), " != (H + 2·Hkv)·", D,
-              " = ", (H + 2 * Hkv) * D, " at head dim ", D);
+  // To = the rows of k_cache; absolute positions run to Tmax = Tp + To behind a prefix of Tp rows
+  const int64_t B = qkv.size(0), Tn = qkv.size(1), Hkv = k_cache.size(1), To = k_cache.size(2), H = n_head;
+  int64_t Tp = 0;
+  TORCH_CHECK(B >= 1 && Tn >= 1 && To >= 1, op, ": empty input");
+  TORCH_CHECK(k_cache.size(0) == B, op, ": cache batch ", k_cache.size(0), " != ", B);
+  TORCH_CHECK(H > 0 && Hkv > 0 && H % Hkv == 0, op, ": need H % Hkv == 0");
+  TORCH_CHECK(qkv.size(2) == (H + 2 * Hkv) * D, op, ": qkv width ", qkv.size(2), " != (H + 2·Hkv)·", D, " = ",
+              (H + 2 * Hkv) * D, " at head dim ", D);
+  if (sh) {
+    TORCH_CHECK(sh->k_prefix.scalar_type() == k_cache.scalar_type() && sh->v_prefix.scalar_type() == k_cache.scalar_type(),
+                op, ": prefix and own caches must have the same dtype (bf16 or float8_e4m3fn)");
+    TORCH_CHECK(sh->k_prefix.dim() == 4 && sh->k_prefix.size(3) == D, op, ": prefix caches of head dim ",
+                sh->k_prefix.dim() == 4 ? sh->k_prefix.size(3) : -1, " with own caches of head dim ", D);
+    check_caches(sh->k_prefix, sh->v_prefix);
+    TORCH_CHECK(sh->v_prefix.sizes() == sh->k_prefix.sizes(), op, ": k_prefix ", sh->k_prefix.sizes(), " and v_prefix ",
+                sh->v_prefix.sizes(), " must have the same shape");
+    Tp = sh->k_prefix.size(2);
+    TORCH_CHECK(sh->group >= 1 && B % sh->group == 0 && sh->k_prefix.size(0) == B / sh->group &&
+                    sh->k_prefix.size(1) == Hkv,
+                op, ": prefix caches must be [B / group, Hkv, Tp, ", D, "] for qkv [B, ...] (B ", B, ", group ", sh->group,
+                ", prefix batch ", sh->k_prefix.size(0), ")");
+    TORCH_CHECK(sh->plen.is_cuda() && sh->plen.get_device() == qkv.get_device() && sh->plen.scalar_type() == at::kLong &&
+                    sh->plen.is_contiguous() && sh->plen.numel() == B / sh->group,
+                op, ": plen must be a contiguous int64 [B / group] tensor on qkv's device");
+    TORCH_CHECK(sh->k_prefix.get_device() == qkv.get_device() && sh->v_prefix.get_device() == qkv.get_device(),
+                op, ": caches must be on qkv's device");
+  }
+  const int64_t Tmax = Tp + To;
   auto chk = [&](const at::Tensor& t, const char* name) {
     TORCH_CHECK(t.is_cuda() && t.get_device() == qkv.get_device() && t.scalar_type() == at::kLong &&
                     t.is_contiguous() && t.numel() == B,
-                "append_attn: ", name, " must be a contiguous int64 [B] tensor on qkv's device");
+                op, ": ", name, " must be a contiguous int64 [B] tensor on qkv's device");
   };
   chk(start, "start");
   chk(nnew, "nnew");
   TORCH_CHECK(k_cache.get_device() == qkv.get_device() && v_cache.get_device() == qkv.get_device(),
-              "append_attn: caches must be on qkv's device");
-  TORCH_CHECK(kv_len_max >= 1 && kv_len_max <= Tmax, "append_attn: kv_len_max must be in [1, Tmax]");
-  TORCH_CHECK(scale > 0, "append_attn: scale must be positive");
-  TORCH_CHECK(key_splits >= 0, "append_attn: key_splits must be 0 (the plan), 1 (never) or a chunk count, got ",
-              key_splits);
+              op, ": caches must be on qkv's device");
+  TORCH_CHECK(kv_len_max >= 1 && kv_len_max <= Tmax, op, ": kv_len_max must be in [1, ", sh ? "Tp + To" : "Tmax", "]");
+  TORCH_CHECK(scale > 0, op, ": scale must be positive");
+  TORCH_CHECK(key_splits >= 0, op, ": key_splits must be 0 (the plan), 1 (never) or a chunk count, got ", key_splits);
   const Rope rp = [&] {
     const bool hc = rope_cos.has_value() && rope_cos->defined(), hs = rope_sin.has_value() && rope_sin->defined();
-    TORCH_CHECK(hc == hs, "append_attn: rope_cos and rope_sin go together");
+    TORCH_CHECK(hc == hs, op, ": rope_cos and rope_sin go together");
     if (!hc) return Rope{nullptr, nullptr};
     TORCH_CHECK(rope_cos->is_cuda() && rope_sin->is_cuda() && rope_cos->get_device() == qkv.get_device() &&
                     rope_sin->get_device() == qkv.get_device() && rope_cos->scalar_type() == at::kFloat &&
                     rope_sin->scalar_type() == at::kFloat && rope_cos->is_contiguous() && rope_sin->is_contiguous() &&
                     rope_cos->dim() == 2 && rope_cos->size(1) == D / 2 && rope_cos->size(0) >= Tmax &&
                     rope_sin->sizes() == rope_cos->sizes(),
-                "append_attn: rope tables must be contiguous float32 [>= Tmax, ", D / 2, "] on qkv's device at head dim ",
-                D);
+                op, ": rope tables must be contiguous float32 [>= ", sh ? "Tp + To" : "Tmax", ", ", D / 2,
+                "] on qkv's device at head dim ", D);
     return Rope{rope_cos->data_ptr<float>(), rope_sin->data_ptr<float>()};
   }();
   const int64_t nqb = (Tn + BLK - 1) / BLK;
   const int64_t total = B * Tn * Hkv * (D / 16);  // append_kv threads
   TORCH_CHECK(B * H * nqb < (1LL << 31) && (total + NT - 1) / NT < (1LL << 31) && Tmax < (1LL << 30) &&
                   Tn < (1LL << 30) && B * H * Tn < (1LL << 40),
-              "append_attn: grid too large");
+              op, ": grid too large");
   at::Tensor out = at::empty({B, Tn, H * D}, qkv.options().memory_format(at::MemoryFormat::Contiguous));
-  AppendParams p;
+  SharedAppendParams p;  // launched whole, or as its AppendParams base (the unshared kernels)
   p.qkv = static_cast<const uint16_t*>(qkv.data_ptr());
   p.sb = qkv.stride(0);
   p.st = qkv.stride(1);
@@ -654,13 +838,19 @@ at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
   p.L = (int)std::min(Tmax, kv_len_max);
   p.nqb = (int)nqb;
   p.sc2 = (float)scale * kLog2e;
+  p.kp = sh ? static_cast<const uint16_t*>(sh->k_prefix.data_ptr()) : nullptr;
+  p.vp = sh ? static_cast<const uint16_t*>(sh->v_prefix.data_ptr()) : nullptr;
+  p.plen = sh ? sh->plen.data_ptr<int64_t>() : nullptr;
+  p.group = sh ? (int)sh->group : 1;
+  p.Tp = (int)Tp;
+  p.To = (int)To;
   // host values only (B, H, Tn, kv_len_max, D): the grids and the workspace are the same on every replay of a graph
   const SplitPlan sp = plan(B * H * nqb, p.L, D, key_splits);
   p.nsplit = sp.nsplit;
   p.chunk_tiles = sp.chunk_tiles;
   p.ws = nullptr;
   const int64_t nwg = B * H * nqb * sp.nsplit, nmerge = B * H * ((Tn + 31) / 32);
-  TORCH_CHECK(nwg < (1LL << 31) && nmerge < (1LL << 31), "append_attn: grid too large");
+  TORCH_CHECK(nwg < (1LL << 31) && nmerge < (1LL << 31), op, ": grid too large");
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(qkv.device());
   at::Tensor ws;  // allocated like `out`; every slot the merge reads is written by this call first
   if (sp.nsplit > 1) {
@@ -668,37 +858,69 @@ at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, con
     p.ws = ws.data_ptr<float>();
   }
   hipStream_t st = c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-  auto launch = [&](auto d_c, auto f8_c) {
+  auto launch = [&](auto d_c, auto f8_c, auto sh_c) {
     constexpr int HD = decltype(d_c)::value;
     constexpr bool F8 = decltype(f8_c)::value;
-    hipLaunchKernelGGL((append_kv_kernel<HD, F8>), dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, p, total);
+    constexpr bool SH = decltype(sh_c)::value;
+    const ParamsOf<SH> q = p;
+    hipLaunchKernelGGL((append_kv_kernel<HD, F8, SH>), dim3((unsigned)((total + NT - 1) / NT)), dim3(NT), 0, st, q, total);
     C10_HIP_KERNEL_LAUNCH_CHECK();
     if (sp.nsplit == 1) {
-      hipLaunchKernelGGL((append_attn_kernel<HD, false, F8>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
+      hipLaunchKernelGGL((append_attn_kernel<HD, false, F8, SH>), dim3((unsigned)nwg), dim3(NT), 0, st, q);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     } else {
-      hipLaunchKernelGGL((append_attn_kernel<HD, true, F8>), dim3((unsigned)nwg), dim3(NT), 0, st, p);
+      hipLaunchKernelGGL((append_attn_kernel<HD, true, F8, SH>), dim3((unsigned)nwg), dim3(NT), 0, st, q);
       C10_HIP_KERNEL_LAUNCH_CHECK();
-      hipLaunchKernelGGL(append_merge_kernel<HD>, dim3((unsigned)nmerge), dim3(NT), 0, st, p);  // fp32 partials only
+      hipLaunchKernelGGL((append_merge_kernel<HD, SH>), dim3((unsigned)nmerge), dim3(NT), 0, st, q);  // fp32 partials only
       C10_HIP_KERNEL_LAUNCH_CHECK();
     }
   };
-  if (D == 64) {
-    if (f8)
-      launch(std::integral_constant<int, 64>{}, std::true_type{});
+  auto launch_d = [&](auto f8_c, auto sh_c) {
+    if (D == 64)
+      launch(std::integral_constant<int, 64>{}, f8_c, sh_c);
     else
-      launch(std::integral_constant<int, 64>{}, std::false_type{});
+      launch(std::integral_constant<int, 128>{}, f8_c, sh_c);
+  };
+  if (sh) {
+    if (f8)
+      launch_d(std::true_type{}, std::true_type{});
+    else
+      launch_d(std::false_type{}, std::true_type{});
   } else {
     if (f8)
-      launch(std::integral_constant<int, 128>{}, std::true_type{});
+      launch_d(std::true_type{}, std::false_type{});
     else
-      launch(std::integral_constant<int, 128>{}, std::false_type{});
+      launch_d(std::false_type{}, std::false_type{});
   }
   return out;
+}
+
+at::Tensor append_attn_hip(const at::Tensor& qkv, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                           const at::Tensor& start, const at::Tensor& nnew, int64_t n_head, double scale,
+                           int64_t kv_len_max, const c10::optional<at::Tensor>& rope_cos,
+                           const c10::optional<at::Tensor>& rope_sin, int64_t key_splits) {
+  return append_run(qkv, k_cache, v_cache, start, nnew, n_head, scale, kv_len_max, rope_cos, rope_sin, key_splits,
+                    nullptr);
+}
+
+// sequence s of qkv [S = B·group, Tn, ...] continues prompt s / group: keys [0, plen[s / group]) are rows of
+// k_prefix / v_prefix [B, Hkv, Tp, D] (read only), the rest its own rows k_own / v_own [S, Hkv, To, D];
+// start [S] counts absolute positions, kv_len_max <= Tp + To
+at::Tensor append_attn_shared_hip(const at::Tensor& qkv, const at::Tensor& k_prefix, const at::Tensor& v_prefix,
+                                  const at::Tensor& plen, const at::Tensor& k_own, const at::Tensor& v_own,
+                                  const at::Tensor& start, const at::Tensor& nnew, int64_t group, int64_t n_head,
+                                  double scale, const c10::optional<at::Tensor>& rope_cos,
+                                  const c10::optional<at::Tensor>& rope_sin, int64_t kv_len_max, int64_t key_splits) {
+  const Shared sh{k_prefix, v_prefix, plen, group};
+  return append_run(qkv, k_own, v_own, start, nnew, n_head, scale, kv_len_max, rope_cos, rope_sin, key_splits, &sh);
 }
 
 }  // namespace attn
 }  // namespace nbd
 
-TORCH_LIBRARY_IMPL(nbd, CUDA, m) { m.impl("append_attn", &nbd::attn::append_attn_hip); }
+TORCH_LIBRARY_IMPL(nbd, CUDA, m) {
+  m.impl("append_attn", &nbd::attn::append_attn_hip);
+  m.impl("append_attn_shared", &nbd::attn::append_attn_shared_hip);
+}
 TORCH_LIBRARY_IMPL(nbd, CompositeExplicitAutograd, m) { m.impl("append_attn_plan", &nbd::attn::append_attn_plan); }
+

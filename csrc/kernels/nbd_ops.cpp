@@ -30,6 +30,11 @@ TORCH_LIBRARY(nbd, m) {
   // a block of new tokens per sequence over the cache (csrc/kernels/append.hip): k | v appended at start[b] + i
   m.def("append_attn(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor start, Tensor nnew, int n_head, "
         "float scale, int kv_len_max, Tensor? rope_cos, Tensor? rope_sin, int key_splits=0) -> Tensor");
+  // the same behind a shared prefix: sequence s of S = B·group continues prompt s / group, whose rows [0, plen) it
+  // reads from the prefix; the block lands in its own rows (start counts absolute positions)
+  m.def("append_attn_shared(Tensor qkv, Tensor k_prefix, Tensor v_prefix, Tensor plen, Tensor(a!) k_own, "
+        "Tensor(b!) v_own, Tensor start, Tensor nnew, int group, int n_head, float scale, Tensor? rope_cos, "
+        "Tensor? rope_sin, int kv_len_max, int key_splits=0) -> Tensor");
   // the key chunks append_attn's plan (key_splits = 0) takes for this problem; 1 = the unsplit kernel
   m.def("append_attn_plan(int batch, int n_head, int Tn, int kv_len_max, int head_dim) -> int");
   m.def("greedy_advance(Tensor logits, Tensor(a!) tok, Tensor(b!) pos, Tensor(c!) out, Tensor(d!)? done, int eos) -> ()");

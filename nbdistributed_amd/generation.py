@@ -23,7 +23,10 @@ The reference's notebooks train; after training, a user of an interactive notebo
 * **several samples per prompt** — ``generate(..., num_return_sequences=R)`` prefills the B
   prompts once into a ``SharedPrefixKVCache`` (each prompt held once, R short tails of own rows)
   and decodes B·R sequences with ``ops.decode_attention_shared``: the same decode kernel, a key's
-  address taken from the prompt's prefix or the sample's own rows.
+  address taken from the prompt's prefix or the sample's own rows.  On a GPU that cache continues
+  like any other — ``generate(turn, n, cache=shared)`` gives each of the B·R samples its own next
+  turn through ``ops.append_attention_shared`` (the block-append kernels' shared-prefix variant),
+  without materialising B·R copies of the prompts.
 
 Models opt in by providing ``kv_layout()``, ``prefill(ids, cache, lengths)``,
 ``decode_step(tok, pos, cache)`` and ``extend(ids, cache, start, nnew)``; see ``models/gpt2.py``
@@ -134,7 +137,9 @@ class SharedPrefixKVCache:
     ``plen[s // group]`` (the prompt's length, int64 [prompts] on the device) and own row
     j - plen from there on.  The surface the models use is ``KVCache``'s: ``t_max`` (the absolute
     capacity t_prefix + t_own: RoPE tables are sized from it), ``store`` (prefill, into the prefix)
-    and ``attend`` (decode, ``ops.decode_attention_shared``).  It cannot be continued."""
+    ``attend`` (decode, ``ops.decode_attention_shared``) and, on a GPU, ``extend`` (continue,
+    ``ops.append_attention_shared``: a turn's rows land in the samples' own rows, so ``t_own`` must
+    hold them — ``generate``'s ``t_max=`` on the first call reserves the room)."""
 
     def __init__(self, n_layer: int, prompts: int, group: int, n_head: int, n_kv: int, t_prefix: int, t_own: int,
                  head_dim: int, dtype=torch.bfloat16, device="cuda"):
@@ -189,9 +194,20 @@ class SharedPrefixKVCache:
                                            self.v_own[layer], pos, self.group, self.n_head, scale=scale, rope=rope,
                                            kv_len_max=self.kv_len_max, workspace=self.workspace)
 
-    def extend(self, *args, **kwargs):
-        raise NotImplementedError("SharedPrefixKVCache.extend: continuing from a shared-prefix cache is not "
-                                  "implemented (the block-append kernel reads one cache per sequence)")
+    def extend(self, layer: int, qkv: torch.Tensor, start: torch.Tensor, nnew: torch.Tensor, rope=None,
+               scale=None) -> torch.Tensor:
+        """Continue: append the ``nnew[s]`` real rows of ``qkv`` [prompts·group, Tn, W] at absolute
+        positions ``start[s]`` to the sequences' own rows and attend each over prefix + own up to
+        itself (``ops.append_attention_shared``).  On a GPU only, for now: a CPU cache raises
+        ``NotImplementedError``."""
+        if not self.k.is_cuda:  # decided before any argument is looked at
+            raise NotImplementedError("SharedPrefixKVCache.extend: continuing from a shared-prefix cache is not "
+                                      "implemented on the CPU (the shared-prefix block-append kernel is a GPU one)")
+        from . import ops
+
+        return ops.append_attention_shared(qkv, self.k[layer], self.v[layer], self.plen, self.k_own[layer],
+                                           self.v_own[layer], start, nnew, self.group, self.n_head, scale=scale,
+                                           rope=rope, kv_len_max=self.kv_len_max)
 
 
 def sample(logits: torch.Tensor, temperature: float = 0.0, top_k: Optional[int] = None,
@@ -297,7 +313,14 @@ def _continue(model, input_ids, max_new_tokens: int, cache: KVCache, lengths, sa
               pad_token_id: int, graph, sync_every: int):
     """``generate`` from a returned cache: the block ``[cache.pending, turn…]`` per sequence goes
     through ``model.extend`` at ``start = cache.lengths``, then the decode loop takes over.  The
-    cache carries its dtype: an fp8 cache is extended and decoded as fp8 (a GPU feature for now)."""
+    cache carries its dtype: an fp8 cache is extended and decoded as fp8 (a GPU feature for now).
+    A ``SharedPrefixKVCache`` (a GPU feature too) continues its prompts·group sequences: the turn's
+    rows and the tokens generated after it land in the samples' own rows, which must hold them."""
+    shared = isinstance(cache, SharedPrefixKVCache)
+    if shared and not cache.k.is_cuda:
+        # the shared-prefix block append exists as a HIP kernel only: refuse before any work
+        raise NotImplementedError("generate: continuing from a shared prefix cache (num_return_sequences > 1) is "
+                                  "not implemented on the CPU")
     if cache.is_fp8 and not cache.k.is_cuda:
         # the fp8 block append exists as a HIP kernel only: refuse before any work
         raise NotImplementedError("generate: continuing from an fp8 cache (kv_dtype='fp8') is not implemented; "
@@ -322,7 +345,16 @@ def _continue(model, input_ids, max_new_tokens: int, cache: KVCache, lengths, sa
     Tn = input_ids.shape[1]
     lens = (torch.full((B,), Tn, dtype=torch.int64, device=device) if lengths is None
             else lengths.to(device=device, dtype=torch.int64))
-    hist = int(cache.lengths.max())  # the one host sync, before any decoding
+    if shared:  # still one host sync: the longest history and the most own rows held, in one transfer
+        own = cache.lengths - cache.plen.repeat_interleave(cache.group)
+        hist, own_held = torch.stack([cache.lengths.max(), own.max()]).tolist()
+        own_need = own_held + 1 + Tn + max_new_tokens  # own rows in use after this call, at most
+        if own_need > cache.t_own:
+            raise ValueError(f"generate: continuing needs {own_need} own rows per sample ({own_held} held + 1 pending "
+                             f"+ {Tn} new + {max_new_tokens} to generate) behind the shared prompts, the cache has "
+                             f"t_own {cache.t_own}: reserve room with t_max= on the first call")
+    else:
+        hist = int(cache.lengths.max())  # the one host sync, before any decoding
     total = hist + 1 + Tn + max_new_tokens  # positions in use after this call (the pending token is one)
     if total > cache.t_max:
         raise ValueError(f"generate: continuing needs {total} cache rows ({hist} held + 1 pending + {Tn} new + "
@@ -457,8 +489,13 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
     short tails, and the decode loop runs at batch B·R with ``ops.decode_attention_shared``.  The
     result is [B·R, T0 + max_new_tokens], row b·R + r laid out as above; the tokens are those of
     the same call on ``input_ids.repeat_interleave(R, 0)`` with the same ``generator``.  The
-    returned cache is the shared one, and cannot be continued (``cache=`` raises
-    ``NotImplementedError``); R > 1 together with ``cache=`` or greedy decoding is a ``ValueError``.
+    returned cache is the shared one.  On a GPU it continues like any other: ``cache=`` it with
+    ``input_ids`` [B·R, Tn], one next turn per sample (greedy allowed: the samples have diverged),
+    and the turn runs through ``ops.append_attention_shared`` over the prompts held once.  The
+    turn's rows and the new tokens land in the samples' own rows: ``t_max=`` on the first call
+    reserves them (own rows = ``t_max`` - the padded prompt length), too few is a ``ValueError``.
+    On the CPU ``cache=`` of a shared cache raises ``NotImplementedError``; R > 1 together with
+    ``cache=`` or greedy decoding is a ``ValueError``.
     """
     kv_dtype = _kv_dtype(kv_dtype)
     R = int(num_return_sequences)
@@ -466,9 +503,6 @@ def generate(model, input_ids: Optional[torch.Tensor], max_new_tokens: int, *,
         raise ValueError(f"generate: num_return_sequences must be >= 1, got {num_return_sequences}")
     if cache is not None and R > 1:
         raise ValueError("generate: num_return_sequences > 1 starts from prompts, not from cache=")
-    if isinstance(cache, SharedPrefixKVCache):
-        raise NotImplementedError("generate: continuing from a shared prefix cache (num_return_sequences > 1) is "
-                                  "not implemented")
     if R > 1:
         if temperature <= 0.0:
             raise ValueError("generate: num_return_sequences > 1 needs temperature > 0 (greedy samples of one "

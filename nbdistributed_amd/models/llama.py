@@ -17,7 +17,8 @@ sequence length that is a multiple of 128; anything else (CPU, fp32) runs the sa
 plain PyTorch.  Head dim 128 (Llama 3.x 3B / 8B, Mistral-7B, Qwen2.5): of the generation kernels
 the per-token one and the block append take it — ``decode_step`` runs ``csrc/kernels/decode.hip``
 at head dim 64 and 128, bf16 and fp8 caches, shared prefix included, and ``extend`` (continue)
-runs ``csrc/kernels/append.hip`` at 64 and 128 on a bf16 cache — while the prefill (flash
+runs ``csrc/kernels/append.hip`` at 64 and 128 on a bf16 or fp8 cache, a shared-prefix cache
+(several samples per prompt) included — while the prefill (flash
 attention) has its kernel at 64 only and runs the PyTorch math at 128.
 
 HF semantics kept by the one-line swap (``native()``):

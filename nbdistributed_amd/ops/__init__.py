@@ -42,6 +42,9 @@ append_attention (K17) a block of new tokens over a KV cache (multi-turn  append
                        128; long histories split over keys; bf16 or      on a host-side plan,
                        fp8 (e4m3, ``q8`` rows) cache, dequantised        append_key_splits; <.., F8>
                        while a tile is staged into LDS                   kernels, kv8.h)
+append_attention_      the same behind a prompt's shared prefix rows: a  append.hip (<.., SHARED>
+shared (K17)           64-key tile comes from the prefix, from the       kernels: one base per tile,
+                       sample's own rows, or (one tile) from both        a per-row select in one)
 =====================  ==============================================  =========================
 
 GPU tensors always go to the HIP kernels; if ``libnbd_ops.so`` cannot be loaded on a GPU box the
@@ -56,7 +59,8 @@ from .attention import PackedBounds, attention_qkv, flash_attention, flash_suppo
 from . import graddst
 from .bucket import (_ref_flatten, _ref_prereduce, _ref_unflatten, bucket_flatten, bucket_unflatten, local_prereduce,
                      plan_offsets, prereduce_into_bucket)
-from .decode import (append_attention, append_attention_reference, append_key_splits, append_supported, decode_attention,
+from .decode import (append_attention, append_attention_reference, append_attention_shared,
+                     append_attention_shared_reference, append_key_splits, append_supported, decode_attention,
                      decode_attention_reference, decode_attention_shared, decode_attention_shared_reference,
                      linear_small, linear_small_reference)
 from .embedding import embedding, embedding_tok_pos
@@ -78,7 +82,7 @@ def __getattr__(name):
 
 
 __all__ = ["linear_tiny", "bucket_flatten", "bucket_unflatten", "local_prereduce", "prereduce_into_bucket", "graddst", "adamw_flat", "cross_entropy", "linear_cross_entropy",
-           "flash_attention", "attention_qkv", "decode_attention", "decode_attention_reference", "decode_attention_shared", "decode_attention_shared_reference", "append_attention", "append_attention_reference", "append_key_splits", "append_supported", "linear_small", "linear_small_reference", "flash_supported", "layer_norm", "add_layer_norm", "linear",
+           "flash_attention", "attention_qkv", "decode_attention", "decode_attention_reference", "decode_attention_shared", "decode_attention_shared_reference", "append_attention", "append_attention_reference", "append_attention_shared", "append_attention_shared_reference", "append_key_splits", "append_supported", "linear_small", "linear_small_reference", "flash_supported", "layer_norm", "add_layer_norm", "linear",
            "colsum", "embedding", "embedding_tok_pos", "gemm_linear", "llama_block", "block_graphs", "block_graphs_memory", "block_graphs_reset", "block_graphs_stats", "cast_buffers_memory", "mlp_gelu", "mlp_swiglu", "rms_norm", "add_rms_norm", "embed_rms_norm", "tokpos_layer_norm", "rope_", "rope_tables", "swiglu", "tensor_summary",
            "tensor_summary_text", "tensor_summary_raw", "plan_offsets", "native_available", "load_library",
            "SUMMARY_FIELDS", "seqcls_prep", "packed_bounds", "PackedBounds"]

@@ -9,7 +9,9 @@ rows and then their own — several samples per prompt with the prompt held once
 Block append (K17, ``csrc/kernels/append.hip``): several new tokens per sequence at per-sequence
 offsets — what continuing from a returned cache runs instead of a second prefill (bf16 or fp8
 cache, head dim 64 or 128).  An fp8 cache holds :func:`q8` rows here too: the new rows are stored
-quantised, and a new token attends over the cache as stored, its own row included.
+quantised, and a new token attends over the cache as stored, its own row included.  Behind a
+shared prefix (``append_attention_shared``): the samples of a prompt continue it from the prefix
+held once, each block landing in its sample's own rows.
 """
 from __future__ import annotations
 
@@ -362,6 +364,115 @@ def append_attention(qkv, k_cache, v_cache, start, nnew, n_head: int, scale: Opt
                                          int(kv_len_max or Tmax), cos, sin,
                                          int(APPEND_KEY_SPLITS if key_splits is None else key_splits))
     return append_attention_reference(qkv, k_cache, v_cache, start, nnew, n_head, sc, rope, kv_len_max)
+
+
+# ------------------------------------------------------------------ block append behind a shared prefix
+def _append_shared_span(plen, start, nnew, group: int, Tn: int, Tp: int, To: int, limit: int):
+    """``plen`` [B], ``start`` / ``nnew`` [B·group] clamped as the kernel clamps them before addressing:
+    0 ≤ plen ≤ Tp, 0 ≤ start - plen ≤ To - 1 (the block never lands in the prefix), 0 ≤ nnew ≤
+    min(Tn, To - (start - plen), limit - start).  Returns (plen per sequence [B·group], start, nnew)."""
+    import torch
+
+    pl = plen.long().clamp(0, Tp).repeat_interleave(group)
+    own0 = (start.long() - pl).clamp(0, To - 1)
+    start = pl + own0
+    nnew = torch.minimum(nnew.long().clamp(0, Tn), torch.minimum(To - own0, limit - start)).clamp(min=0)
+    return pl, start, nnew
+
+
+def append_attention_shared_reference(qkv, k_prefix, v_prefix, plen, k_own, v_own, start, nnew, group: int,
+                                      n_head: int, scale: Optional[float] = None, rope=None,
+                                      kv_len_max: Optional[int] = None):
+    """PyTorch version of :func:`append_attention_shared`, in :func:`append_attention_reference`'s
+    conventions (fp32 math — fp64 when ``qkv`` is float64; writes the own caches the same way, never
+    the prefix; on fp8 caches the new rows are stored as :func:`q8` makes them and the block attends
+    over the caches as stored)."""
+    import torch
+
+    S, Tn, W = qkv.shape
+    Hkv, To, D = k_own.shape[1], k_own.shape[2], k_own.shape[3]
+    Tp, Tmax = k_prefix.shape[2], k_prefix.shape[2] + k_own.shape[2]
+    H, G = n_head, n_head // Hkv
+    dev = qkv.device
+    ft = torch.float64 if qkv.dtype == torch.float64 else torch.float32
+    sc = float(scale) if scale is not None else D ** -0.5
+    pl, start, nnew = _append_shared_span(plen, start, nnew, group, Tn, Tp, To, min(Tmax, int(kv_len_max or Tmax)))
+    i = torch.arange(Tn, device=dev)
+    valid = i[None, :] < nnew[:, None]  # [S, Tn]
+    pos = (start[:, None] + i[None, :]).clamp(max=Tmax - 1)  # (clamped only on padding rows)
+    q = qkv[..., : H * D].reshape(S, Tn, H, D).to(ft)
+    k = qkv[..., H * D:(H + Hkv) * D].reshape(S, Tn, Hkv, D).to(ft)
+    v = qkv[..., (H + Hkv) * D:].reshape(S, Tn, Hkv, D)
+    if rope is not None:
+        half = D // 2
+        c, s = rope[0][pos][:, :, None, :].to(ft), rope[1][pos][:, :, None, :].to(ft)
+
+        def rot(x):
+            a, b = x[..., :half], x[..., half:]
+            return torch.cat([a * c - b * s, b * c + a * s], -1)
+
+        q, k = rot(q), rot(k)
+    bi, ti = valid.nonzero(as_tuple=True)
+    k_own[bi, :, pos[bi, ti] - pl[bi]] = _to_cache(k[bi, ti], k_own.dtype)
+    v_own[bi, :, pos[bi, ti] - pl[bi]] = _to_cache(v[bi, ti], v_own.dtype)
+    # logical key j of sequence s: prefix[s // group, :, j] below plen, own[s, :, j - plen] from there on;
+    # keys >= start + nnew hold nothing of this sequence (possibly NaN): zeros, and masked below
+    t = torch.arange(Tmax, device=dev)
+    si = torch.arange(S, device=dev)
+    in_pre = (t[None, :] < pl[:, None])[:, None, :, None]  # [S, 1, Tmax, 1]
+    held = (t[None, :] < (start + nnew)[:, None])[:, None, :, None]
+
+    def logical(pre, own):
+        m = own.float().to(ft)[si[:, None], :, (t[None, :] - pl[:, None]).clamp(0, To - 1)].transpose(1, 2)
+        if Tp:
+            m = torch.where(in_pre, pre.float().to(ft)[si // group][:, :, t.clamp(max=Tp - 1)], m)
+        return torch.where(held, m, torch.zeros((), dtype=ft, device=dev))  # [S, Hkv, Tmax, D]
+
+    kc, vc = logical(k_prefix, k_own), logical(v_prefix, v_own)
+    s = torch.einsum("btkgd,bksd->bkgts", q.reshape(S, Tn, Hkv, G, D), kc) * sc  # [S, Hkv, G, Tn, Tmax]
+    mask = t[None, None, :] > pos[:, :, None]  # [S, Tn, Tmax]
+    p = torch.softmax(s.masked_fill(mask[:, None, None], float("-inf")), -1)
+    o = torch.einsum("bkgts,bksd->btkgd", p, vc).reshape(S, Tn, H * D)
+    return o.masked_fill(~valid[:, :, None], 0.0).to(qkv.dtype)
+
+
+def append_attention_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, start, nnew, group: int, n_head: int,
+                            scale: Optional[float] = None, rope=None, kv_len_max: Optional[int] = None,
+                            key_splits: Optional[int] = None):
+    """:func:`append_attention` where ``group`` consecutive sequences continue one prompt held once.
+
+    ``qkv`` [S = B·group, Tn, (H + 2·Hkv)·D]; sequence s belongs to prompt s // group.  Its logical key
+    j is ``k_prefix[s // group, :, j]`` ([B, Hkv, Tp, D], read only) for j < ``plen[s // group]``
+    (int64 [B] on the device) and ``k_own[s, :, j - plen]`` ([S, Hkv, To, D]) from there on.
+    ``start`` int64 [S] counts absolute positions (prefix + own rows already valid): for i < nnew[s]
+    the new k (rotated at ``start[s] + i``) and v are written to own row ``start[s] + i - plen`` and
+    query i attends logical keys 0..start[s] + i.  ``plen`` is clamped to [0, Tp], ``start - plen``
+    to [0, To - 1] and ``nnew`` to [0, min(Tn, To - (start - plen), limit - start)] first, with
+    ``limit`` = min(Tp + To, ``kv_len_max``) (a host bound on max(start + nnew), default Tp + To).
+    Prefix rows ≥ plen and own rows ≥ start - plen + nnew influence nothing, whatever they hold.
+    ``key_splits`` as in :func:`append_attention`.  Returns [S, Tn, H·D] with exact zeros on the
+    padding rows — bit for bit what :func:`append_attention` returns on the materialised cache
+    (prefix rows copied in front of each sequence's own rows).  GPU, bf16 qkv, bf16 or fp8 caches
+    (prefix and own alike), head dim 64 or 128 → ``csrc/kernels/append.hip`` (the ``SHARED``
+    kernels); elsewhere :func:`append_attention_shared_reference`."""
+    D = k_own.shape[-1]
+    sc = float(scale) if scale is not None else D ** -0.5
+    if k_prefix.dtype != k_own.dtype or v_prefix.dtype != k_own.dtype or v_own.dtype != k_own.dtype:
+        raise ValueError(f"append_attention_shared: prefix ({k_prefix.dtype}) and own ({k_own.dtype}) caches "
+                         f"must have the same dtype")
+    if append_supported(qkv, k_own, n_head, v_own) and k_prefix.shape[-1] == D:
+        _require()
+        import torch
+
+        T = k_prefix.shape[2] + k_own.shape[2]
+        cos, sin = rope if rope is not None else (None, None)
+        if qkv.stride(-1) != 1 or qkv.stride(0) % 8 or qkv.stride(1) % 8 or qkv.data_ptr() % 16:
+            qkv = qkv.contiguous()
+        return torch.ops.nbd.append_attn_shared(qkv, k_prefix, v_prefix, plen, k_own, v_own, start, nnew, int(group),
+                                                int(n_head), sc, cos, sin, int(kv_len_max or T),
+                                                int(APPEND_KEY_SPLITS if key_splits is None else key_splits))
+    return append_attention_shared_reference(qkv, k_prefix, v_prefix, plen, k_own, v_own, start, nnew, group, n_head,
+                                             sc, rope, kv_len_max)
 
 
 # ------------------------------------------------------------------ small-M fused linear (K14)
