@@ -484,6 +484,53 @@ def head_dim_bench(a):
             json.dump(res, f, indent=1)
 
 
+def smallm_stream_bench(a):
+    """``--smallm-stream``: ms per token of eager ``decode_step`` on the Llama-3.2-3B-shaped stack of
+    ``--layers`` layers with the MLP's linears on the op-by-op path (``NBD_SMALLM_STREAM=0``) against the
+    streaming kernel (``=1``); the switch is set per arm in one process, rounds interleaved."""
+    import statistics
+    from unittest import mock
+
+    from nbdistributed_amd import ops
+    from nbdistributed_amd.generation import KVCache
+    from nbdistributed_amd.models.llama import LlamaConfig, LlamaForCausalLM
+
+    res = {"what": f"ms per token, Llama-3.2-3B-shaped stack of {a.layers} layers (hidden 3072, intermediate 8192, head dim "
+                   f"128), random bf16 weights, eager decode_step at history 512; NBD_SMALLM_STREAM 0 vs 1, rounds interleaved",
+           "layers": a.layers, "rounds": a.rounds, "points": []}
+    torch.manual_seed(0)
+    cfg = LlamaConfig(vocab_size=32000, hidden_size=3072, intermediate_size=8192, num_hidden_layers=a.layers,
+                      num_attention_heads=24, num_key_value_heads=8, max_position_embeddings=8192, explicit_head_dim=128)
+    m = LlamaForCausalLM(cfg).to("cuda", torch.bfloat16).eval()
+    steps, hist = 16, 512
+    for B in [int(x) for x in a.batches.split(",")]:
+        cache = KVCache.for_model(m, B, hist + 64)
+        for t in (cache.k, cache.v):
+            t.copy_(torch.randn(t.shape, device="cuda", dtype=torch.bfloat16))
+        tok = torch.randint(1, 32000, (B,), device="cuda")
+        pos = torch.full((B,), hist, device="cuda", dtype=torch.int64)
+        ms = {"0": [], "1": []}
+        for _ in range(a.rounds + 1):  # the first round warms up
+            for arm in ms:
+                with mock.patch.object(ops.decode, "SMALLM_STREAM", arm):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for i in range(steps):
+                        m.decode_step(tok, pos + i, cache)
+                    torch.cuda.synchronize()
+                    ms[arm].append((time.perf_counter() - t0) * 1e3 / steps)
+        row = dict(batch=B, history=hist)
+        for arm, t in ms.items():
+            row[f"stream{arm}_ms_per_token"] = round(statistics.median(t[1:]), 4)
+            row[f"stream{arm}_min_max"] = [round(min(t[1:]), 4), round(max(t[1:]), 4)]
+        print(json.dumps(row), flush=True)
+        res["points"].append(row)
+        del cache
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def head_dim_continue_bench(a):
     """``--continue --head-dim 128``: the time to the first token of turn 2 on the Llama-3.2-3B-shaped
     stack of ``head_dim_bench``, three arms in one process with their rounds interleaved —
@@ -937,12 +984,16 @@ def main():
     ap.add_argument("--new", type=int, default=256)
     ap.add_argument("--no-hf", action="store_true")
     ap.add_argument("--model", default="gpt2", choices=["gpt2", "smollm2"])
+    ap.add_argument("--smallm-stream", dest="smallm_stream", action="store_true",
+                    help="the MLP linears' streaming kernel (NBD_SMALLM_STREAM=1) against the op-by-op path (=0)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from nbdistributed_amd import ops
     from nbdistributed_amd.models import GPT2, GPT2Config
 
     ops.load_library()
+    if a.smallm_stream:
+        return smallm_stream_bench(a)
     if a.shared and a.cont:
         if a.batches == "1,8,32":
             a.batches = "4"

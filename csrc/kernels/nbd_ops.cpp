@@ -39,7 +39,9 @@ TORCH_LIBRARY(nbd, m) {
   m.def("append_attn_plan(int batch, int n_head, int Tn, int kv_len_max, int head_dim) -> int");
   m.def("greedy_advance(Tensor logits, Tensor(a!) tok, Tensor(b!) pos, Tensor(c!) out, Tensor(d!)? done, int eos) -> ()");
   m.def("linear_small(Tensor x, Tensor w, Tensor? bias, Tensor? norm_w, Tensor? norm_b, float eps, int norm, "
-        "int act, Tensor? residual) -> Tensor");
+        "int act, Tensor? residual, int stream=0) -> Tensor");
+  // the K-slices linear_small's streaming kernel takes at stream = 0 (0 = it refuses: normalise separately)
+  m.def("linear_small_plan(int M, int N, int K, int norm, int act) -> int");
   m.def("attn_merge_(Tensor(a!) o_acc, Tensor(b!) lse_acc, Tensor o_b, Tensor lse_b, Tensor(c!)? out=None) -> ()");
   m.def("ln_fwd(Tensor x, Tensor? delta, Tensor weight, Tensor bias, float eps) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("ln_bwd(Tensor x, Tensor dy, Tensor? dres, Tensor weight, Tensor mean, Tensor rstd) -> (Tensor, Tensor, Tensor)");

@@ -32,52 +32,10 @@
 #include <algorithm>
 
 #include "nbd_common.h"
+#include "smallm.h"
 
 namespace nbd {
 namespace smallm {
-
-constexpr int NT = 512;
-constexpr int NW = NT / kWave;  // 8 waves
-constexpr int XPAD = 8;         // bf16 elements of row padding in the LDS x image (bank spread)
-
-enum Norm { NORM_NONE = 0, NORM_LN = 1, NORM_RMS = 2 };
-enum Act { ACT_NONE = 0, ACT_GELU = 1, ACT_SWIGLU = 2 };
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef short s8v __attribute__((ext_vector_type(8)));
-
-struct Args {
-  const uint16_t* x;  // [M, K] bf16, row stride ldx
-  int64_t ldx;
-  const uint16_t* w;  // [N_w, K] bf16 contiguous
-  const uint16_t* bias;  // [N] or nullptr
-  const uint16_t* nw;    // norm γ [K] or nullptr
-  const uint16_t* nb;    // LayerNorm β [K] or nullptr
-  const uint16_t* res;   // [M, N] or nullptr (row stride N)
-  uint16_t* out;         // [M, N]
-  int M, N, K, norm, stage, ntiles, up_off;  // stage: x image in LDS; up_off: SwiGLU's first up row
-  float eps;
-};
-
-__device__ __forceinline__ float gelu_tanh(float x) {
-  const float u = 0.7978845608028654f * (x + 0.044715f * x * x * x);
-  return x * __fdividef(1.f, 1.f + __expf(-2.f * u));
-}
-__device__ __forceinline__ float silu(float x) { return x * __fdividef(1.f, 1.f + __expf(-x)); }
-
-__device__ __forceinline__ void unpack8(const u32x4& w, float (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    v[2 * j] = __uint_as_float(w[j] << 16);
-    v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-  }
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
 
 // the x image xs[MT·16][K + XPAD] in LDS, rows [0, M) only (the MFMA loop substitutes zeros for
 // the rest): every thread loads its 16-B pieces of the whole [M, K] block at once (one memory
@@ -274,8 +232,6 @@ __global__ __launch_bounds__(NT) void linear_small_kernel(Args a) {
   }
 }
 
-constexpr size_t kMaxLds = 160 * 1024;
-
 static size_t lds_bytes(int MT, int K, bool stage, int act, int norm) {
   const size_t xs = stage ? (size_t)MT * 16 * (K + XPAD) * 2 : 0;
   const size_t gb = norm != NORM_NONE ? (size_t)2 * K * 2 : 0;
@@ -284,7 +240,8 @@ static size_t lds_bytes(int MT, int K, bool stage, int act, int norm) {
 
 at::Tensor linear_small_hip(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias,
                             const c10::optional<at::Tensor>& norm_w, const c10::optional<at::Tensor>& norm_b,
-                            double eps, int64_t norm, int64_t act, const c10::optional<at::Tensor>& residual) {
+                            double eps, int64_t norm, int64_t act, const c10::optional<at::Tensor>& residual,
+                            int64_t stream) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 &&
                   x.stride(0) % 8 == 0 && ((uintptr_t)x.data_ptr() & 15) == 0,
               "linear_small: x must be a bf16 [M, K] GPU view with unit last stride and 16-B aligned rows");
@@ -293,8 +250,13 @@ at::Tensor linear_small_hip(const at::Tensor& x, const at::Tensor& w, const c10:
               "linear_small: w must be a contiguous bf16 [N, K] GPU tensor");
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(M >= 1 && M <= 64, "linear_small: 1 <= M <= 64 rows");
-  TORCH_CHECK(K == w.size(1) && K % 32 == 0 && K <= (act == ACT_SWIGLU ? 2048 : 4096),
-              "linear_small: K must match w, K % 32 == 0, K <= 4096 (2048 with SwiGLU)");
+  TORCH_CHECK(K == w.size(1) && K % 32 == 0 && K <= kStreamMaxK,
+              "linear_small: K must match w, K % 32 == 0, K <= ", kStreamMaxK);
+  // stream: 0 = this unit's kernel wherever it takes the shape (K <= 4096, 2048 with SwiGLU) and
+  // the streaming kernel (smallm_stream.hip) with its plan's K-slices beyond; n >= 1 = the
+  // streaming kernel with n K-slices at any shape
+  TORCH_CHECK(stream >= 0 && stream <= kStreamMaxSlices && stream <= K / 32, "linear_small: stream = ", stream,
+              " K-slices, but at most ", kStreamMaxSlices, " and at most K / 32 = ", K / 32, " (one MFMA step each)");
   TORCH_CHECK(norm >= 0 && norm <= 2 && act >= 0 && act <= 2, "linear_small: bad norm / act");
   const bool swiglu = act == ACT_SWIGLU;
   TORCH_CHECK(!swiglu || w.size(0) % 2 == 0, "linear_small: SwiGLU needs w = [gate; up]");
@@ -328,6 +290,20 @@ at::Tensor linear_small_hip(const at::Tensor& x, const at::Tensor& w, const c10:
   a.ntiles = (int)((N + 15) / 16);
   a.up_off = (int)N;
   a.eps = (float)eps;
+  if (stream > 0 || K > (swiglu ? 2048 : 4096)) {
+    const int S = stream > 0 ? (int)stream : stream_plan((int)M, (int)N, (int)K, (int)norm, (int)act);
+    TORCH_CHECK(S > 0 && (norm == NORM_NONE || stream_lds_bytes((int)M, (int)K, S, (int)act, true) <= kMaxLds),
+                "linear_small: the norm prologue's x slice [", M, ", K / ", S, "] does not fit in 160 KiB of LDS; ",
+                "normalise separately");
+    // the slices' fp32 partial tiles: allocated like out, so the call stays graph-capturable
+    at::Tensor ws;
+    if (S > 1) ws = at::empty({S, swiglu ? 2 : 1, M, N}, x.options().dtype(at::kFloat));
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+    launch_stream(a, (int)act, S, S > 1 ? ws.data_ptr<float>() : nullptr,
+                  c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream(), (int)x.get_device());
+    C10_HIP_KERNEL_LAUNCH_CHECK();
+    return out;
+  }
   // m-tiles per workgroup: all of them (weights read once) unless the x image would not fit in
   // LDS, or the column tiles alone leave most CUs idle — then one m-tile per workgroup and a
   // second grid dimension over the row groups (the weights are re-read from L2)
@@ -373,7 +349,15 @@ at::Tensor linear_small_hip(const at::Tensor& x, const at::Tensor& w, const c10:
   return out;
 }
 
+int64_t linear_small_plan(int64_t M, int64_t N, int64_t K, int64_t norm, int64_t act) {
+  TORCH_CHECK(M >= 1 && M <= 64 && N >= 1 && K >= 32 && K % 32 == 0 && K <= kStreamMaxK && norm >= 0 && norm <= 2 &&
+                  act >= 0 && act <= 2,
+              "linear_small_plan: 1 <= M <= 64, K % 32 == 0, K <= ", kStreamMaxK);
+  return stream_plan((int)M, (int)N, (int)K, (int)norm, (int)act);
+}
+
 }  // namespace smallm
 }  // namespace nbd
 
 TORCH_LIBRARY_IMPL(nbd, CUDA, m) { m.impl("linear_small", &nbd::smallm::linear_small_hip); }
+TORCH_LIBRARY_IMPL(nbd, CompositeExplicitAutograd, m) { m.impl("linear_small_plan", &nbd::smallm::linear_small_plan); }

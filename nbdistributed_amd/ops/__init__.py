@@ -30,8 +30,13 @@ decode_attention (K13) one-token attention over a KV cache: RoPE +      decode.h
                        dim 64 or 128
 decode_attention_      the same over a prompt's shared prefix rows plus  decode.hip (decode_kernel
 shared (K13)           the sample's own rows (several samples / prompt)  <D, G, F8, SHARED>)
-linear_small (K14)     decode linear: LN/RMS prologue + x·Wᵀ (MFMA) +   smallm.hip
-                       bias / GELU / SwiGLU / residual epilogue, M ≤ 64
+linear_small (K14)     decode linear: LN/RMS prologue + x·Wᵀ (MFMA) +   smallm.hip (K ≤ 4096, 2048
+                       bias / GELU / SwiGLU / residual epilogue, M ≤ 64  with SwiGLU: weights in
+                                                                         registers); smallm_stream.hip
+                                                                         (K ≤ 32768: K-slices over
+                                                                         workgroups, a register ring;
+                                                                         NBD_SMALLM_STREAM=1 only: it
+                                                                         lost to the library GEMM)
 packed_bounds (K16)    position_ids of packed rows -> per-query start /  packed.hip (one wave per
                        per-key end of the document, for the document-    row); attn.hip SEG kernels
                        masked K7 kernels (attention_qkv(bounds=))

@@ -485,13 +485,32 @@ def _lds_bytes(M: int, K: int, norm: int, act: int) -> int:
     return (mt * 16 * (K + 8) * 2 + 4 * K if norm else 0) + 8 * (2 if act == 2 else 1) * mt * 256 * 4
 
 
+STREAM_MAX_K = 32768  # smallm_stream.hip: K is bounded by indexing only
+
+
+def _streams(K: int, act: str) -> bool:
+    """Past what smallm.hip keeps in registers: the streaming kernel's range."""
+    return K > (2048 if act == "swiglu" else 4096)
+
+
 def linear_small_supported(x, w, norm=None, act: str = "none") -> bool:
+    """Whether ``torch.ops.nbd.linear_small`` takes this call: smallm.hip up to K = 4096 (2048 with
+    SwiGLU), smallm_stream.hip beyond, up to ``STREAM_MAX_K`` — there a norm prologue is taken when
+    the kernel's plan finds K-slices whose x image fits in LDS (``linear_small_plan`` > 0)."""
     import torch
 
     M, K = x.shape
-    return (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and 1 <= M <= 64
-            and K % 32 == 0 and K <= (2048 if act == "swiglu" else 4096) and x.stride(-1) == 1
-            and _lds_bytes(M, K, _NORM[norm[0] if norm else None], _ACT[act]) <= 160 * 1024)
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and 1 <= M <= 64
+            and K % 32 == 0 and x.stride(-1) == 1):
+        return False
+    nk, ak = _NORM[norm[0] if norm else None], _ACT[act]
+    if not _streams(K, act):
+        return _lds_bytes(M, K, nk, ak) <= 160 * 1024
+    if K > STREAM_MAX_K:
+        return False
+    _require()
+    N = w.shape[0] // 2 if act == "swiglu" else w.shape[0]
+    return int(torch.ops.nbd.linear_small_plan(int(M), int(N), int(K), nk, ak)) > 0
 
 
 def _apply_norm(x, norm):
@@ -534,12 +553,39 @@ LIBRARY_MIN_N = 16384
 LIBRARY_MIN_ROWS = 4
 
 
-def linear_small(x, w, bias=None, norm=None, act: str = "none", residual=None):
+def _stream_mode(value: Optional[str]) -> str:
+    v = (value or "auto").strip().lower()
+    if v not in ("auto", "0", "1"):
+        raise ValueError(f"NBD_SMALLM_STREAM must be auto, 0 or 1, got {value!r}")
+    return v
+
+
+# ``NBD_SMALLM_STREAM``, for the shapes past smallm.hip's K (4096, 2048 with SwiGLU): ``0`` = the
+# op-by-op path (library GEMM and separate norm / SwiGLU / add kernels), ``1`` = always the
+# streaming kernel (smallm_stream.hip), ``auto`` = the streaming kernel up to STREAM_MAX_ROWS rows.
+SMALLM_STREAM = _stream_mode(os.environ.get("NBD_SMALLM_STREAM"))
+# Measured on MI355X (benchmarks/smallm_bench.py --stream, profiles/smallm_stream_bench.json,
+# docs/FINDINGS.md §51), graph-replayed, per shape class (the op's ``act``): the most rows at which
+# the streaming kernel's median beat the op-by-op path's by more than that path's spread on every
+# model shape measured; -1 = on none, or not measured (GELU past K = 4096: no model has it).
+STREAM_MAX_ROWS = {"none": -1, "swiglu": -1, "gelu": -1}
+
+
+def _stream_routed(M: int, act: str) -> bool:
+    return SMALLM_STREAM == "1" or (SMALLM_STREAM == "auto" and M <= STREAM_MAX_ROWS[act])
+
+
+def linear_small(x, w, bias=None, norm=None, act: str = "none", residual=None, stream: Optional[int] = None):
     """``residual + act(norm(x) · Wᵀ + bias)`` for a few token rows (decode), one HIP kernel.
 
     ``x`` [M ≤ 64, K]; ``w`` [N, K] (``act="swiglu"``: [gate; up] = [2N, K], out = silu(g)·u);
     ``norm`` = ``("ln", γ, β, eps)`` or ``("rms", γ, eps)`` applied to x first; ``residual``
-    [M, N].  GPU bf16 → ``csrc/kernels/smallm.hip``; elsewhere the same math in PyTorch."""
+    [M, N].  GPU bf16 → ``csrc/kernels/smallm.hip`` up to K = 4096 (2048 with SwiGLU) and
+    ``csrc/kernels/smallm_stream.hip`` beyond (K ≤ 32768), where ``NBD_SMALLM_STREAM`` and
+    ``STREAM_MAX_ROWS`` decide between that kernel and the separate ops; elsewhere the same math
+    in PyTorch.  ``stream``: ``None`` = that routing; an integer goes to the op as it is and takes
+    the HIP path wherever the op accepts the shape — ``0`` = the plan's K-slices past smallm.hip's
+    K, ``n ≥ 1`` = the streaming kernel with n K-slices at any K."""
     import torch
     import torch.nn.functional as F
 
@@ -550,13 +596,14 @@ def linear_small(x, w, bias=None, norm=None, act: str = "none", residual=None):
         x, norm = _apply_norm(x, norm), None
     if x.is_cuda and M >= LIBRARY_MIN_ROWS and w.shape[0] >= LIBRARY_MIN_N and act == "none" and residual is None:
         return F.linear(x if norm is None else _apply_norm(x, norm), w, bias)
-    if linear_small_supported(x, w, norm, act):
+    wanted = stream is not None or not _streams(x.shape[1], act) or _stream_routed(M, act)
+    if wanted and linear_small_supported(x, w, norm, act):
         _require()
         nk = _NORM[norm[0] if norm else None]
         nw = norm[1] if norm else None
         nb = norm[2] if norm and norm[0] == "ln" else None
         eps = float(norm[-1]) if norm else 0.0
-        return torch.ops.nbd.linear_small(x, w, bias, nw, nb, eps, nk, _ACT[act], residual)
+        return torch.ops.nbd.linear_small(x, w, bias, nw, nb, eps, nk, _ACT[act], residual, int(stream or 0))
     # the same steps as separate ops (more rows than the kernel takes, CPU, other dtypes)
     from .llama import swiglu
 
